@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — MCTS self-play throughput of the batched engine on MI355X.  ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` on its own re-executes itself through torch.distributed.run with N ranks.)
 
@@ -407,6 +407,47 @@ def net_check_timed_leaves(eng, net, module, blob, dev, n_f64=256):
     return out
 
 
+DUMP_SAMPLE_SLOTS = 512        # records of a fixed, seeded sample of the batch's slots (the whole batch's are ~150 MB at 8192 games)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def timed_outputs(eng):
+    """What a caller of the timed path receives, as the last timed step left it: the net's answers in the leaf exchange
+    (policy, value; rows the step did not evaluate are zeroed) and the game records (per recorded move: root visit counts,
+    action, n, q; plies beyond a slot's n_plies are zero) of DUMP_SAMPLE_SLOTS slots drawn with a fixed seed, with
+    n_plies and status of every slot.  float32 / float64 arrays keyed by file name."""
+    import numpy as np
+    ex = eng.leaf_exchange()
+    active = ex["active"].cpu().numpy() != 0
+    policy = ex["policy"].cpu().numpy()
+    value = ex["value"].cpu().numpy()
+    raw = eng.read_raw()
+    n = eng.n_games
+    pick = np.sort(np.random.default_rng(0).choice(n, min(DUMP_SAMPLE_SLOTS, n), replace=False))
+    hdr = raw["headers"][pick]
+    out = {"leaf_active": active.astype(np.float32),
+           "leaf_policy": np.where(active[:, None], policy, 0.0).astype(np.float32),
+           "leaf_value": np.where(active, value, 0.0).astype(np.float32),
+           "record_slots": pick.astype(np.float64),
+           "record_root_n": raw["root_n"][pick].astype(np.float32),
+           "record_action": hdr["action"].astype(np.float64), "record_n": hdr["n"].astype(np.float64),
+           "record_q": hdr["q"].astype(np.float64),
+           "n_plies": raw["n_plies"].astype(np.float64), "status": raw["status"].astype(np.float64)}
+    if raw["root_w"] is not None:
+        out["record_root_w"] = raw["root_w"][pick].astype(np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise AssertionError(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def headline_leg(args, dev, rank, world, cdev, group=False):
     import numpy as np
     import torch
@@ -470,6 +511,8 @@ def headline_leg(args, dev, rank, world, cdev, group=False):
     elapsed = time.perf_counter() - t0
     st = eng.stats()
     c1 = eng.leaf_cache_stats()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_outputs(eng))
     net_check = None
     if rank == 0 and not args.no_spotcheck and "f16x3" in (net.kernel_name or "") and not args.fused:
         net_check = net_check_timed_leaves(eng, net, module, blob, dev)
@@ -1422,7 +1465,11 @@ def main():
                          "(the default run takes ~7 min on an MI355X box; on a slower box legs are dropped from the end, each with a note, "
                          "instead of the line arriving late or not at all)")
     ap.add_argument("--full-out", default=None, help="where the full document goes (default: gpurun_out/bench_full.json if gpurun_out/ exists, else ./bench_full.json)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (rank 0; see timed_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

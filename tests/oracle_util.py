@@ -20,6 +20,19 @@ def load_par_golden():
     return load_mcts_golden("mcts_par_games.json")
 
 
+def load_differential_golden():
+    """What the unmodified reference answered on the seeded inputs of the differential tests (make_golden_differential.py)."""
+    return load_mcts_golden("reference_differential.json")
+
+
+def ply_digest(root_n, root_w):
+    """sha256 (16 hex digits) of a ply's root N and root W as float64 bytes, -0.0 read as 0.0 (equal under ==)."""
+    import numpy as np
+    n = np.asarray(root_n, dtype=np.float64) + 0.0
+    w = np.asarray(root_w, dtype=np.float64) + 0.0
+    return hashlib.sha256(n.tobytes() + w.tobytes()).hexdigest()[:16]
+
+
 def orc_cfg_of(game):
     """OrcPlayCfg of a golden game, with the parallel_search_num the reference ran it at."""
     return O.play_cfg_from_config(config_of(game), parallel_search_num=game["resolved_play"]["parallel_search_num"])

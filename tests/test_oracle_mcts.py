@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import oracle as O
-from oracle_util import load_mcts_golden, load_par_golden, orc_cfg_of, golden_net_blob, config_of, dense, rows_of_game
+from oracle_util import (load_mcts_golden, load_par_golden, load_differential_golden, orc_cfg_of, golden_net_blob, config_of, dense,
+                         rows_of_game, ply_digest)
 
 
 @pytest.fixture(scope="module")
@@ -173,19 +174,29 @@ def check_play_rows(golden, blob):
         assert hashlib.sha256(json.dumps(rows).encode()).hexdigest() == g["play_rows_sha256"], g["variant"]
 
 
-@pytest.mark.needs_reference
-def test_live_reference_game_matches_oracle(blob):
-    """A fresh differential run (new seed/config) against the imported reference, container only."""
-    import ref_harness as rh
-    import ref_selfplay as rs
-    cfg = rh.load_config("alpha_go_zero.yml", {"play": {"parallel_search_num": 1, "c_puct": 1.5, "noise_eps": 0.4,
-                                                         "dirichlet_alpha": 1.0, "change_tau_turn": 6}})
-    ref = rs.run_reference_game(cfg, blob, seed=99, game_id=123456, sims_per_move=15)
-    plies, summ = O.selfplay_game(O.play_cfg_from_config(cfg), blob, 99, 123456, 15)
-    assert [p["action"] for p in plies] == [p["action"] for p in ref["plies"]]
-    for a, b in zip(plies, ref["plies"]):
-        assert a["root_n"] == b["root_n"] and a["root_w"] == b["root_w"]
-    assert summ["winner"] == ref["winner"]
+@pytest.fixture(scope="module")
+def ref_games():
+    """Whole games of the unmodified reference worker on fixed seeds and overrides (tests/golden/make_golden_differential.py)."""
+    return {g["name"]: g for g in load_differential_golden()["games"]}
+
+
+def check_reference_game(g, blob, start=None):
+    """The oracle plays golden game g (same seed, game id, simulations, play settings): every action, player and root N / W
+    (float64, digest) and the winner == the reference's."""
+    cfg = config_of(g)
+    plies, summ = O.selfplay_game(O.play_cfg_from_config(cfg, parallel_search_num=g["parallel_search_num"]), blob, g["seed"], g["game_id"],
+                                  g["sims"], **({} if start is None else {"start": start}))
+    assert [p["action"] for p in plies] == g["actions"], g["name"]
+    assert [p["player"] for p in plies] == g["players"], g["name"]
+    for i, p in enumerate(plies):
+        assert ply_digest(p["root_n"], p["root_w"]) == g["root_digests"][i], (g["name"], "ply", i)
+    assert summ["winner"] == g["winner"], g["name"]
+    return plies, summ
+
+
+def test_live_reference_game_matches_oracle(blob, ref_games):
+    """A game at a seed and config of its own (alpha_go_zero.yml, c_puct 1.5, noise_eps 0.4, dirichlet_alpha 1.0, change_tau_turn 6)."""
+    check_reference_game(ref_games["live_agz"], blob)
 
 
 def test_gamma_sampler_above_one_has_the_gamma_distribution():
@@ -203,28 +214,15 @@ def test_gamma_sampler_above_one_has_the_gamma_distribution():
     assert abs(v.sum() - 1.0) < 1e-12 and (v > 0).sum() == 6
 
 
-@pytest.mark.needs_reference
-def test_reference_game_at_dirichlet_alpha_above_one_matches_oracle(blob):
+def test_reference_game_at_dirichlet_alpha_above_one_matches_oracle(blob, ref_games):
     """The unmodified reference with dirichlet_alpha = 2.0 (np.random.dirichlet served by the raz-rng-v1 stream) == the oracle."""
-    import ref_harness as rh
-    import ref_selfplay as rs
-    cfg = rh.load_config("alpha_go_zero.yml", {"play": {"parallel_search_num": 1, "noise_eps": 0.5, "dirichlet_alpha": 2.0}})
-    ref = rs.run_reference_game(cfg, blob, seed=31, game_id=77, sims_per_move=12)
-    plies, summ = O.selfplay_game(O.play_cfg_from_config(cfg), blob, 31, 77, 12)
-    assert [p["action"] for p in plies] == [p["action"] for p in ref["plies"]]
-    for a, b in zip(plies, ref["plies"]):
-        assert a["root_n"] == b["root_n"] and a["root_w"] == b["root_w"]
+    check_reference_game(ref_games["dirichlet_alpha_2"], blob)
 
 
-@pytest.mark.needs_reference
-def test_game_taken_up_at_a_position_matches_the_reference(blob):
+def test_game_taken_up_at_a_position_matches_the_reference(blob, ref_games):
     """orc_selfplay_game_from (bench.py's check of its steady-state batch): the reference worker whose env is put on a
     mid-game position by ReversiEnv.update (env/reversi_env.py:33-40) instead of reset() plays, with fresh players and
     fresh random streams, the game the oracle plays from that position - white and black to move, with a pass on the way."""
-    import ref_harness as rh
-    import ref_selfplay as rs
-    cfg = rh.load_config("ch5.yml", {"play": {"parallel_search_num": 1, "thinking_loop": 1, "use_solver_turn": 0,
-                                              "use_solver_turn_in_simulation": 0}})
     env = O.OrcEnv()
     lib = O.load()
     rng = np.random.default_rng(3)
@@ -240,31 +238,22 @@ def test_game_taken_up_at_a_position_matches_the_reference(blob):
         starts.append((int(env.black), int(env.white), int(env.next_player)))
     assert {s[2] for s in starts} == {1, 2}
     for k, st in enumerate(starts):
-        ref = rs.run_reference_game(cfg, blob, seed=5, game_id=900 + k, sims_per_move=14, start=st)
-        plies, summ = O.selfplay_game(O.play_cfg_from_config(cfg), blob, 5, 900 + k, 14, start=st)
-        assert [p["action"] for p in plies] == [p["action"] for p in ref["plies"]] and len(plies) >= 5
-        for a, b in zip(plies, ref["plies"]):
-            assert a["root_n"] == b["root_n"] and a["root_w"] == b["root_w"] and a["player"] == b["player"]
-        assert summ["winner"] == ref["winner"]
+        g = ref_games[f"from_position_{k}"]
+        assert [int(g["start"][0], 16), int(g["start"][1], 16), g["start"][2]] == list(st)   # the position the reference was put on
+        plies, _ = check_reference_game(g, blob, start=st)
+        assert len(plies) >= 5
     # from the initial position it is the ordinary game
+    cfg = config_of(ref_games["from_position_0"])
     a = O.selfplay_game(O.play_cfg_from_config(cfg), blob, 5, 77, 9, start=(0x0000000810000000, 0x0000001008000000, 1))
     assert a == O.selfplay_game(O.play_cfg_from_config(cfg), blob, 5, 77, 9)
 
 
-@pytest.mark.needs_reference
-def test_live_reference_parallel_search_matches_oracle(blob):
-    """Fresh differential runs at parallel_search_num 5 and 7 (not in the goldens), container only."""
-    import ref_harness as rh
-    import ref_selfplay as rs
-    for k, yml, seed in ((5, "mini.yml", 77), (7, "alpha_go_zero.yml", 78)):
-        cfg = rh.load_config(yml, {"play": {"parallel_search_num": k, "reset_mtcs_info_per_game": 1,
-                                            "use_solver_turn": 0, "use_solver_turn_in_simulation": 0}})
-        ref = rs.run_reference_game(cfg, blob, seed=seed, game_id=4242, sims_per_move=18, virtual_time=True)
-        plies, summ = O.selfplay_game(O.play_cfg_from_config(cfg, parallel_search_num=k), blob, seed, 4242, 18)
-        assert [p["action"] for p in plies] == [p["action"] for p in ref["plies"]]
-        for a, b in zip(plies, ref["plies"]):
-            assert a["root_n"] == b["root_n"] and a["root_w"] == b["root_w"]
-        assert summ["n_expand"] == ref["nn_positions"] and summ["winner"] == ref["winner"]
+def test_live_reference_parallel_search_matches_oracle(blob, ref_games):
+    """Games at parallel_search_num 5 (mini.yml) and 7 (alpha_go_zero.yml), not in the other goldens."""
+    for name in ("par5_mini", "par7_agz"):
+        g = ref_games[name]
+        _, summ = check_reference_game(g, blob)
+        assert summ["n_expand"] == g["nn_positions"], name
 
 
 @pytest.mark.needs_reference

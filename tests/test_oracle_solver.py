@@ -3,7 +3,7 @@ tests/golden/solver_kat.json holds the answers of the reference's COMPILED Cytho
 reference's own three known answers (lib/reversi_solver.py:102-156: q1 -> (57, +2), q2 -> (4 or 14, -2), q3 -> (3, +2))
 and for 120 late-game positions in both modes.  CPU: oracle/orc_solver.c == those answers; GPU: the device solver
 (solver_solve in csrc/raz_engine.hip, reached through raz_engine_set_position on the KAT boards) == those answers;
-needs_reference: a fresh sweep against the live Cython solver."""
+and 40 further positions against the Cython solver's answers in tests/golden/reference_differential.json."""
 import ctypes
 import json
 import os
@@ -51,33 +51,16 @@ def test_oracle_solver_equals_compiled_cython_on_golden_positions(kat):
         assert _orc_solve(b, w, pl, False) == p["non_exact"], p
 
 
-@pytest.mark.needs_reference
 def test_oracle_solver_vs_live_cython_sweep():
-    """Fresh positions (not in the golden file) against the imported, compiled reference solver - container only."""
-    import random
-    import ref_harness as rh
-    rh.install()
-    import pyximport
-    pyximport.install(build_dir="/tmp/pyxbld_raz", language_level=3)
-    from reversi_zero.lib.alt.reversi_solver_cython import ReversiSolver
-    from reversi_zero.env.reversi_env import ReversiEnv, Player
-    from reversi_zero.lib.bitboard import find_correct_moves, bit_count
-    rng = random.Random(777)
-    done = 0
-    while done < 40:
-        env = ReversiEnv().reset()
-        stop_at = 64 - rng.randint(2, 9)
-        while not env.done and bit_count(env.board.black) + bit_count(env.board.white) < stop_at:
-            own, enemy = env.get_own_and_enemy()
-            legal = find_correct_moves(own, enemy)
-            env.step(rng.choice([i for i in range(64) if legal >> i & 1]))
-        if env.done:
-            continue
-        b, w, pl = env.board.black, env.board.white, env.next_player.value
-        for exactly in (True, False):
-            m, s = ReversiSolver().solve(b, w, Player(pl), timeout=300, exactly=exactly)
-            assert _orc_solve(b, w, pl, exactly) == [m, s]
-        done += 1
+    """Positions not in solver_kat.json (random(777) playouts of the reference env) against the compiled reference solver's
+    answers in both modes (tests/golden/make_golden_differential.py)."""
+    from oracle_util import load_differential_golden
+    positions = load_differential_golden()["solver_random777"]
+    assert len(positions) == 40
+    for p in positions:
+        b, w, pl = int(p["black"], 16), int(p["white"], 16), p["next_player"]
+        assert _orc_solve(b, w, pl, True) == p["exact"], p
+        assert _orc_solve(b, w, pl, False) == p["non_exact"], p
 
 
 @pytest.mark.gpu

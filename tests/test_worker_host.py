@@ -89,18 +89,21 @@ def test_schedule_and_force_sim(tmp_path):
     assert default_block_games(blob(16), 4096) == 65536 and default_block_games(blob(256), 8192) == 32768 and default_block_games(None, 100) == 400
 
 
-@pytest.mark.needs_reference
-def test_config_overlay_matches_reference_yml():
+def test_config_overlay_matches_reference_yml(tmp_path):
     """Loading the reference's own yml files gives the same play/play_data/model values as the
-    reference Config overlay."""
-    import ref_harness as rh
+    reference Config overlay; both stored in tests/golden/reference_differential.json."""
+    import yaml
+    from oracle_util import load_differential_golden
     from reversi_alpha_zero_amd.config import load_config
-    for yml in ("mini.yml", "ch5.yml", "alpha_go_zero.yml"):
-        mine = load_config(os.path.join(rh.REFERENCE_ROOT, "config", yml))
-        ref = rh.load_config(yml)
+    golden = load_differential_golden()["config_overlay"]
+    assert sorted(golden) == ["alpha_go_zero.yml", "ch5.yml", "mini.yml"]
+    for yml, g in golden.items():
+        path = tmp_path / yml
+        path.write_text(yaml.safe_dump(g["yml"]))
+        mine = load_config(str(path))
         for sec in ("play", "play_data", "model"):
-            a, b = getattr(mine, sec), getattr(ref, sec)
-            for k, v in vars(b).items():
+            a, b = getattr(mine, sec), g["resolved"][sec]
+            for k, v in b.items():
                 got = getattr(a, k)
                 assert (list(map(list, got)) if k.startswith("schedule") else got) == \
                        (list(map(list, v)) if k.startswith("schedule") else v), (yml, sec, k)

@@ -13,7 +13,7 @@ NAME=${3:-prof_$MODE}
 PASSES=${4:-"stats 1 2 3 4"}
 shift; shift; shift; shift
 EXTRA="$*"
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$NAME
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
