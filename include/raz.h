@@ -111,6 +111,9 @@ typedef struct {
     size_t weight_bytes;
 } raz_net;
 
+/* Largest value_fc the library takes: the head kernels keep (192 + value_fc) floats of the position in LDS and stay within the
+ * default 64 KB of dynamic LDS a launch may use.  A wider value head is refused (raz_net_weight_bytes 0, raz_net_load RAZ_EINVAL). */
+#define RAZ_NET_MAX_VALUE_FC 16192
 size_t raz_net_weight_bytes(int filters, int res_layers, int value_fc); /* 0 = unsupported shape */
 size_t raz_net_scratch_bytes(int filters, int value_fc, size_t n);      /* HBM scratch for n positions */
 int raz_net_load(raz_net* net, const void* blob, size_t blob_bytes, void* d_weights, size_t d_bytes,
@@ -122,19 +125,41 @@ int raz_net_load(raz_net* net, const void* blob, size_t blob_bytes, void* d_weig
 int raz_net_forward(const raz_net* net, const uint64_t* own, const uint64_t* enemy,
                     const uint8_t* active, float* policy, float* value, size_t n, void* scratch,
                     size_t scratch_bytes, raz_stream_t stream);
+/* Which kernel form raz_net_forward runs a batch of n positions of `net` on (raz_net_forward takes its choice from this function):
+ *   RAZ_NET_FORM_MFMA             k_net_mfma (filters 16 / 32 / 64, value_fc <= 1024; reserved 0)
+ *   RAZ_NET_FORM_MFMA_WAVE        the same kernel asked for as the one-wave-per-position test variant (reserved 2)
+ *   RAZ_NET_FORM_WAVE_LDS         k_net_wave, activations in LDS (reserved 1, or a shape no matrix-core kernel takes, when
+ *                                 (3 * 64 * filters + 192 + value_fc) floats fit 64 KB)
+ *   RAZ_NET_FORM_WAVE_SCRATCH     k_net_wave, activations in the caller's scratch (the same, when they do not fit)
+ *   RAZ_NET_FORM_WIDE             k_conv0_wide + k_conv3x3_wide + k_heads_wide (filters >= 128, % 64 == 0; reserved 0 or 2)
+ *   RAZ_NET_FORM_F16X3_REPAIR     raznet-forward-v2 (reserved 4) with the in-forward repair of rows out of the f16 range
+ *   RAZ_NET_FORM_F16X3_NO_REPAIR  raznet-forward-v2 without it (see raz_net_range_check)
+ * Negative (RAZ_EINVAL) for a NULL net or a `reserved` raz_net_forward refuses.  No device work. */
+#define RAZ_NET_FORM_MFMA 1
+#define RAZ_NET_FORM_MFMA_WAVE 2
+#define RAZ_NET_FORM_WAVE_LDS 3
+#define RAZ_NET_FORM_WAVE_SCRATCH 4
+#define RAZ_NET_FORM_WIDE 5
+#define RAZ_NET_FORM_F16X3_REPAIR 6
+#define RAZ_NET_FORM_F16X3_NO_REPAIR 7
+int raz_net_form(const raz_net* net, size_t n);
 
 /* raz_net.reserved selects the forward kernels: 0 = the exact-f32 kernels chosen by shape ("raznet-forward-v1": every output
  * one k-ordered fmaf chain, bit-identical to the CPU oracle); 4 (filters % 128 == 0) = "raznet-forward-v2": the 3x3 trunk on
  * the f16 matrix cores with every f32 operand split into two halfs (csrc/raz_net_f16x3.hip: 3 f16 MFMAs per product, f32
  * accumulation, within 1e-5 of the fp32 graph, 16/3 of the f32-MFMA rate); 1, 2: test variants of v1 (same bits).  v2's split activations must
- * stay inside the f16 range: a row (position) whose activations do not is evaluated by the exact-f32 chains inside the same
- * forward; *overflowed = 1 reports that some forward since raz_net_load had more such rows than it repairs (32; sticky): run the
- * net with reserved = 0 then.  Synchronises `stream`. */
+ * stay inside the f16 range.  Where a row's f32 activations fit a CU's LDS ((2 * 64 * filters + 192 + value_fc) floats <= 160 KB:
+ * filters 128, and 256 with value_fc <= 8000 - raz_net_form RAZ_NET_FORM_F16X3_REPAIR) a row (position) whose activations do not
+ * is evaluated by the exact-f32 chains inside the same forward, and *overflowed = 1 reports that some forward since raz_net_load
+ * had more such rows than it repairs (32; sticky).  On the other v2 shapes (RAZ_NET_FORM_F16X3_NO_REPAIR: filters >= 384, or
+ * 256 with a wider value head) NO row is repaired: a single row out of range raises the sticky flag, that row's outputs cannot be
+ * trusted, the other rows' can.  Either way: run the net with reserved = 0 once *overflowed = 1.  Synchronises `stream`. */
 int raz_net_range_check(const raz_net* net, int* overflowed, raz_stream_t stream);
 /* The same plus *rows_repaired: v2 rows (positions) since raz_net_load whose activations left the f16 range and were therefore
  * evaluated by the exact-f32 chains instead, inside the forward that met them (at most 32 rows per forward; a forward with more
- * raises the sticky flag reported by *overflowed).  A row's answer is a function of its position alone either way.  No reference
- * counterpart (Keras computes in fp32 throughout, agent/api.py:30-45).  Synchronises `stream`. */
+ * raises the sticky flag reported by *overflowed; always 0 on the RAZ_NET_FORM_F16X3_NO_REPAIR shapes).  Where rows are repaired a
+ * row's answer is a function of its position alone either way.  No reference counterpart (Keras computes in fp32 throughout,
+ * agent/api.py:30-45).  Synchronises `stream`. */
 int raz_net_range_stats(const raz_net* net, int* overflowed, unsigned long long* rows_repaired, raz_stream_t stream);
 
 /* ---- batched self-play engine --------------------------------------------------------------------

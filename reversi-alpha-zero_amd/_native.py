@@ -96,6 +96,7 @@ SIGNATURES.update({
     "raz_net_load": (c_int, [POINTER(RazNet), ctypes.c_char_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "raz_net_forward": (c_int, [POINTER(RazNet), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p, c_size_t, c_void_p]),
+    "raz_net_form": (c_int, [POINTER(RazNet), c_size_t]),
     "raz_net_range_check": (c_int, [POINTER(RazNet), POINTER(c_int), c_void_p]),
     "raz_net_range_stats": (c_int, [POINTER(RazNet), POINTER(c_int), POINTER(ctypes.c_ulonglong), c_void_p]),
     "raz_engine_workspace_bytes": (c_size_t, [POINTER(RazEngineConfig)]),

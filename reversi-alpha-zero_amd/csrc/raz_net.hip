@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64) void k_net_wave_repair(const float* __restrict_
 }  // namespace
 
 extern "C" size_t raz_net_weight_bytes(int filters, int res_layers, int value_fc) {
-    if (filters <= 0 || filters % 16 || res_layers < 0 || value_fc <= 0) return 0;
+    if (filters <= 0 || filters % 16 || res_layers < 0 || value_fc <= 0 || value_fc > RAZ_NET_MAX_VALUE_FC) return 0;
     return total_floats(filters, res_layers, value_fc) * sizeof(float);
 }
 
@@ -270,6 +270,8 @@ extern "C" int raz_net_load(raz_net* net, const void* blob, size_t blob_bytes, v
     const int F = h[2], R = h[3], V = h[4];
     if (F <= 0 || F % 16 || R < 0 || V <= 0)
         return raz_fail(RAZ_EINVAL, "raz_net_load: filters must be a positive multiple of 16");
+    if (V > RAZ_NET_MAX_VALUE_FC)   // the heads' LDS ((192 + V) floats) would pass the default 64 KB a launch may take
+        return raz_fail(RAZ_EINVAL, "raz_net_load: value_fc above RAZ_NET_MAX_VALUE_FC");
     const size_t nsrc = ((size_t)F * 18 + F) + (size_t)R * 2 * ((size_t)F * F * 9 + F) + (2 * (size_t)F + 2) +
                         (128 * 64 + 64) + ((size_t)F + 1) + (64 * (size_t)V + V) + ((size_t)V + 1);
     if (blob_bytes != 32 + 4 * nsrc) return raz_fail(RAZ_EINVAL, "raz_net_load: blob size mismatch");
@@ -401,6 +403,25 @@ int raz_net_forward_compact(const raz_net* net, const uint64_t* own, const uint6
     return raz_net_forward(net, own, enemy, active, policy, value, n, scratch, scratch_bytes, (raz_stream_t)stream);
 }
 
+// The one place that decides which kernels a forward runs on (raz_net_forward dispatches on its answer).
+extern "C" int raz_net_form(const raz_net* net, size_t n) {
+    (void)n;   // (no form depends on the batch size today)
+    if (!net) return raz_fail(RAZ_EINVAL, "raz_net_form: NULL argument");
+    const int F = net->filters, V = net->value_fc, rs = net->reserved;
+    if (rs != 0 && rs != 1 && rs != 2 && rs != 4)
+        return raz_fail(RAZ_EINVAL, "raz_net_forward: raz_net.reserved must be 0, 1, 2 or 4 (5 and 6 selected kernels that were removed in ABI 3)");
+    // reserved (tests): 1 forces the VALU kernel, 2 the one-wave-per-position MFMA kernel
+    if (raz_net_mfma_supported(F, V) && rs != 1) return rs == 2 ? RAZ_NET_FORM_MFMA_WAVE : RAZ_NET_FORM_MFMA;
+    // reserved 4: raznet-forward-v2 - the trunk on the f16 matrix cores with split operands (raz_net_f16x3.hip), within 1e-5
+    // of the fp32 graph but not bit-identical to the exact-f32 kernels (0 / 5: raznet-forward-v1)
+    if (rs == 4) {
+        if (!f16x3_supported(F)) return raz_fail(RAZ_EINVAL, "raz_net_forward: the f16x3 kernel needs filters % 128 == 0");
+        return f16x3_repairs(F, V) ? RAZ_NET_FORM_F16X3_REPAIR : RAZ_NET_FORM_F16X3_NO_REPAIR;
+    }
+    if (wide_supported(F) && rs != 1) return RAZ_NET_FORM_WIDE;
+    return use_lds(F, V) ? RAZ_NET_FORM_WAVE_LDS : RAZ_NET_FORM_WAVE_SCRATCH;
+}
+
 extern "C" int raz_net_forward(const raz_net* net, const uint64_t* own, const uint64_t* enemy,
                                const uint8_t* active, float* policy, float* value, size_t n,
                                void* scratch, size_t scratch_bytes, raz_stream_t stream) {
@@ -408,28 +429,31 @@ extern "C" int raz_net_forward(const raz_net* net, const uint64_t* own, const ui
     if (!net || !net->d_weights || !own || !enemy || !policy || !value)
         return raz_fail(RAZ_EINVAL, "raz_net_forward: NULL argument");
     const int F = net->filters, V = net->value_fc;
-    if (net->reserved != 0 && net->reserved != 1 && net->reserved != 2 && net->reserved != 4)
-        return raz_fail(RAZ_EINVAL, "raz_net_forward: raz_net.reserved must be 0, 1, 2 or 4 (5 and 6 selected kernels that were removed in ABI 3)");
-    // reserved (tests): 1 forces the VALU kernel, 2 the one-wave-per-position MFMA kernel
-    if (raz_net_mfma_supported(F, V) && net->reserved != 1)
-    {
-        // debug: RAZ_NET_PROF=1 and a caller scratch of >= n*64 bytes -> per-position phase ticks
-        unsigned long long* prof = nullptr;
-        if (scratch && scratch_bytes >= n * 64 && getenv("RAZ_NET_PROF")) prof = (unsigned long long*)scratch;
-        return raz_net_forward_mfma((const float*)net->d_weights, F, net->res_layers, V, own, enemy, active, policy,
-                                    value, n, (hipStream_t)stream, prof);
+    const float* W = (const float*)net->d_weights;
+    const int form = raz_net_form(net, n);
+    switch (form) {
+        case RAZ_NET_FORM_MFMA:
+        case RAZ_NET_FORM_MFMA_WAVE: {
+            // debug: RAZ_NET_PROF=1 and a caller scratch of >= n*64 bytes -> per-position phase ticks
+            unsigned long long* prof = nullptr;
+            if (scratch && scratch_bytes >= n * 64 && getenv("RAZ_NET_PROF")) prof = (unsigned long long*)scratch;
+            return raz_net_forward_mfma(W, F, net->res_layers, V, own, enemy, active, policy, value, n, (hipStream_t)stream, prof);
+        }
+        case RAZ_NET_FORM_F16X3_REPAIR:
+        case RAZ_NET_FORM_F16X3_NO_REPAIR:
+            return raz_net_forward_f16x3(W, F, net->res_layers, V, own, enemy, active, policy, value, n, scratch, scratch_bytes,
+                                         (hipStream_t)stream, nullptr, nullptr);
+        case RAZ_NET_FORM_WIDE:
+            return raz_net_forward_wide(W, F, net->res_layers, V, own, enemy, active, policy, value, n, scratch, scratch_bytes,
+                                        (hipStream_t)stream);
+        case RAZ_NET_FORM_WAVE_LDS:
+        case RAZ_NET_FORM_WAVE_SCRATCH:
+            break;
+        default:
+            return form;   // (RAZ_EINVAL, recorded)
     }
-    // reserved 4: raznet-forward-v2 - the trunk on the f16 matrix cores with split operands (raz_net_f16x3.hip), within 1e-5
-    // of the fp32 graph but not bit-identical to the exact-f32 kernels (0 / 5: raznet-forward-v1)
-    if (f16x3_supported(F) && net->reserved == 4)
-        return raz_net_forward_f16x3((const float*)net->d_weights, F, net->res_layers, V, own, enemy, active, policy, value, n,
-                                     scratch, scratch_bytes, (hipStream_t)stream, nullptr, nullptr);
-    if (net->reserved == 4) return raz_fail(RAZ_EINVAL, "raz_net_forward: the f16x3 kernel needs filters % 128 == 0");
-    if (wide_supported(F) && net->reserved != 1)
-        return raz_net_forward_wide((const float*)net->d_weights, F, net->res_layers, V, own, enemy, active, policy,
-                                    value, n, scratch, scratch_bytes, (hipStream_t)stream);
     NetDims d = {F, net->res_layers, V};
-    const bool lds = use_lds(F, V);
+    const bool lds = form == RAZ_NET_FORM_WAVE_LDS;
     if (!lds) {
         if (!scratch || scratch_bytes < raz_net_scratch_bytes(F, V, n))
             return raz_fail(RAZ_ENOMEM, "raz_net_forward: scratch too small (raz_net_scratch_bytes)");
@@ -437,11 +461,11 @@ extern "C" int raz_net_forward(const raz_net* net, const uint64_t* own, const ui
     const size_t shm = lds_bytes_for(F, V, lds);
     if (lds)
         hipLaunchKernelGGL(k_net_wave<true>, dim3((unsigned)n), dim3(64), shm, (hipStream_t)stream,
-                           (const float*)net->d_weights, d, (const raz_bb*)own, (const raz_bb*)enemy, active,
+                           W, d, (const raz_bb*)own, (const raz_bb*)enemy, active,
                            policy, value, (float*)scratch, (int)n);
     else
         hipLaunchKernelGGL(k_net_wave<false>, dim3((unsigned)n), dim3(64), shm, (hipStream_t)stream,
-                           (const float*)net->d_weights, d, (const raz_bb*)own, (const raz_bb*)enemy, active,
+                           W, d, (const raz_bb*)own, (const raz_bb*)enemy, active,
                            policy, value, (float*)scratch, (int)n);
     return raz_check_launch("raz_net_forward");
 }

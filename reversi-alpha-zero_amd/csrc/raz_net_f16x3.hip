@@ -417,7 +417,7 @@ int raz_net_heads_split(const float* W, int F, int R, int V, const unsigned char
 // two activation buffers, then a 64-byte area per row for its range flag (raz_internal.h raz_net_repair_rows): linear in n
 size_t raz_net_f16x3_scratch_bytes(int F, size_t n) { return n * ((size_t)2 * F * 256 + RAZ_NET_ROWFLAG_WORDS * 4); }
 
-// F > 256 (a row's f32 activations do not fit a CU's LDS, so there is no in-forward repair): any row out of range raises the sticky flag
+// !f16x3_repairs(F, V) (a row's f32 activations do not fit a CU's LDS, so there is no in-forward repair): any row out of range raises the sticky flag
 __global__ __launch_bounds__(256) void k_flag_unrepaired(const unsigned* __restrict__ rowflag, unsigned* __restrict__ sticky, int n,
                                                          const uint32_t* __restrict__ n_ptr) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -473,7 +473,7 @@ int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* o
     if (rc != RAZ_OK) return rc;
     // rows whose activations left the f16 range: the same position through the exact-f32 chains (raznet-forward-v1), so a row's
     // answer is a function of its position alone - v2's when it stays in range, v1's when it does not
-    if (((size_t)2 * F * 64 + 192 + (size_t)V) * sizeof(float) > 160 * 1024)   // (F > 256: a row does not fit a CU's LDS - not repaired, see raz_net_range_check)
+    if (!f16x3_repairs(F, V))   // (F > 256, or 256 with V > 8000: a row does not fit a CU's LDS - not repaired, see raz_net_range_check)
         return raz_net_flag_unrepaired(flag, sticky, n, n_ptr, s);
     return raz_net_repair_rows(W, F, R, V, own, enemy, policy, value, n, flag, sticky, list, n_ptr, s);
 }

@@ -41,6 +41,9 @@ RAZ_HD_LAYOUT size_t wide_tile_off(int F, int R, int V, int l, int c, int nt) { 
 //   kernel is 24,576 contiguous bytes in exactly its LDS image order (lane-linear 16-byte units for global_load_lds).  Then
 //   2R floats: 1 / S_l per layer.
 RAZ_HD_LAYOUT bool f16x3_supported(int F) { return F >= 128 && F % 128 == 0; }
+// raznet-forward-v2 repairs a row out of the f16 range in the same forward only where the row's f32 activations (two buffers) and
+// the heads' scratch fit the 160 KB of LDS of a CU (k_net_wave_repair); elsewhere such a row only raises the sticky flag
+RAZ_HD_LAYOUT bool f16x3_repairs(int F, int V) { return ((size_t)2 * F * 64 + 192 + (size_t)V) * 4 <= 160 * 1024; }
 RAZ_HD_LAYOUT size_t f16x3_off(int F, int R, int V) { return (wide_off(F, R, V) + (size_t)2 * R * wide_layer_floats(F) + 63) / 64 * 64; }
 RAZ_HD_LAYOUT size_t f16x3_layer_off(int F, int R, int V, int l) { return f16x3_off(F, R, V) + (size_t)(l - 1) * wide_layer_floats(F); }  // l >= 1
 RAZ_HD_LAYOUT size_t f16x3_scale_off(int F, int R, int V) { return f16x3_off(F, R, V) + (size_t)2 * R * wide_layer_floats(F); }

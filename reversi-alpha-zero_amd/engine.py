@@ -29,6 +29,10 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+# include/raz.h RAZ_NET_FORM_*
+FORMS = {1: "mfma", 2: "mfma_wave", 3: "wave_lds", 4: "wave_scratch", 5: "wide", 6: "f16x3_repair", 7: "f16x3_no_repair"}
+
+
 class DeviceNet:
     """The policy/value net resident in HBM (agent/api.py ReversiModelAPI role, device side)."""
 
@@ -63,6 +67,13 @@ class DeviceNet:
         if need and (self._scratch is None or self._scratch.numel() < need):
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return (self._scratch.data_ptr(), self._scratch.numel()) if need else (None, 0)
+
+    def form(self, n=1):
+        """The kernel form a forward of n positions runs on (include/raz.h raz_net_form): one of FORMS' names."""
+        f = lib.raz_net_form(ctypes.byref(self.c), n)
+        if f < 0:
+            check(f, "raz_net_form")
+        return FORMS[f]
 
     def range_ok(self):
         """False when a split-f16 activation left the f16 range since the net was loaded (raz_net_range_check)."""

@@ -172,3 +172,41 @@ def test_integration_md_names_every_entry_point():
             slashed.add(prefix + "_" + part.lstrip("_"))
     missing = [n for n in names if n not in doc and n not in slashed]
     assert not missing, missing
+
+
+def test_net_value_head_wider_than_the_heads_lds_is_refused():
+    """include/raz.h RAZ_NET_MAX_VALUE_FC: the head kernels keep (192 + value_fc) floats in LDS within the default 64 KB of a launch;
+    one unit more is refused before any device work - raz_net_weight_bytes 0, raz_net_load RAZ_EINVAL, DeviceNet ValueError - so
+    that no over-limit launch can happen.  The widest accepted head runs on the GPU (tests/test_net_shapes_gpu.py)."""
+    import ctypes
+    import struct
+    from reversi_alpha_zero_amd import _native as N
+    from reversi_alpha_zero_amd.agent.model import blob_float_count
+    from reversi_alpha_zero_amd.engine import DeviceNet
+    top = 16192
+    assert (192 + top) * 4 == 64 * 1024
+    for F in (16, 48, 128, 256):
+        assert N.lib.raz_net_weight_bytes(F, 1, top) > 0
+        assert N.lib.raz_net_weight_bytes(F, 1, top + 1) == 0
+    blob = struct.pack("<8i", 0x4E5A4152, 1, 16, 1, top + 1, 3, 0, 0) + bytes(4 * blob_float_count(16, 1, top + 1))
+    dummy = (ctypes.c_uint8 * 64)()
+    net = N.RazNet()
+    assert N.lib.raz_net_load(ctypes.byref(net), blob, len(blob), ctypes.addressof(dummy), 1 << 40, None) == -1
+    assert "value_fc" in N.last_error()
+    with pytest.raises(ValueError):
+        DeviceNet(blob, "cpu")
+
+
+def test_net_form_names_the_kernels_of_every_shape():
+    """raz_net_form (the choice raz_net_forward dispatches on) over the edges of the table in include/raz.h; no device work."""
+    import ctypes
+    from reversi_alpha_zero_amd import _native as N
+
+    def form(F, V, reserved):
+        net = N.RazNet(filters=F, res_layers=1, value_fc=V, reserved=reserved)
+        return N.lib.raz_net_form(ctypes.byref(net), 1)
+    assert [form(16, 1024, 0), form(16, 1024, 2), form(16, 1024, 1), form(16, 1025, 0)] == [1, 2, 3, 3]
+    assert [form(80, 832, 0), form(80, 833, 0), form(96, 1, 0), form(144, 7, 0)] == [3, 4, 4, 4]   # (3*64*80 + 192 + 832) * 4 B = 64 KB
+    assert [form(128, 64, 0), form(128, 64, 2), form(128, 64, 1), form(192, 7, 0), form(192, 7, 4)] == [5, 5, 4, 5, -1]
+    assert [form(128, 16192, 4), form(256, 8000, 4), form(256, 8001, 4), form(384, 1, 4), form(16, 16, 4)] == [6, 6, 7, 7, 1]
+    assert form(16, 16, 3) == -1 and "reserved" in N.last_error()

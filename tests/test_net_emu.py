@@ -163,3 +163,54 @@ def test_emulated_rows_that_leave_the_f16_range_are_evaluated_by_the_exact_f32_c
     assert np.array_equal(pol[~crowded].view(np.uint32), sp.view(np.uint32)) and np.array_equal(val[~crowded].view(np.uint32), sv.view(np.uint32))
     assert st2 == {"overflowed": False, "rows_repaired": 0}
     assert st == {"overflowed": n_crowded > 32, "rows_repaired": n_crowded}
+
+
+# CPU twins of tests/test_net_shapes_gpu.py on the cheap shapes: R = 0, the value-width edges of the narrow nets, F = 192 wide
+EMU_CASES = [((16, 0, 1), 0, 1), ((16, 1, 1025), 0, 3), ((64, 0, 1025), 0, 3), ((80, 1, 1025), 0, 4), ((32, 2, 7), 2, 2),
+             ((112, 0, 1), 0, 4), ((192, 1, 1025), 0, 5), ((128, 1, 4096), 4, 6)]
+
+
+def _sharp_rows():
+    import net_cases as C
+    own, enemy, names = C.inputs(n_random=3)
+    rows = [0, 1, 2, names.index("empty"), names.index("full"), names.index("own@0"), names.index("enemy@63"),
+            names.index("own@7"), names.index("overlap all"), len(names) - 1]
+    return own, enemy, names, rows
+
+
+@pytest.mark.parametrize("shape,reserved,form", EMU_CASES, ids=lambda c: "x".join(map(str, c)) if isinstance(c, tuple) else str(c))
+def test_emulated_forms_on_edge_shapes_against_f64(lib, shape, reserved, form):
+    """Each case's form (include/raz.h raz_net_form) on a sharp net (tests/net_cases.py: the f64 reference is guarded against
+    degenerate heads) over the edge boards: exact-f32 forms == the oracle bit for bit on every row, the f16x3 trunk within 1e-5 of
+    f64, output rows past n left alone (a NaN guard row)."""
+    import net_cases as C
+    from reversi_alpha_zero_amd import _native as N
+    F, R, V = shape
+    own_all, enemy_all, names, rows = _sharp_rows()
+    own, enemy = own_all[rows], enemy_all[rows]
+    net = C.sharp_net(F, R, V, F + R, own, enemy)
+    rp, rv = C.reference(net, own, enemy)
+    C.assert_sharp(rp, rv, str(shape))
+    blob = net.to_blob()
+    w = np.zeros(lib.raz_net_weight_bytes(F, R, V), dtype=np.uint8)
+    dn = N.RazNet()
+    dn.reserved = reserved
+    assert lib.raz_net_load(ctypes.byref(dn), blob, len(blob), w.ctypes.data, w.size, None) == 0, lib.raz_last_error()
+    lib.raz_net_form.restype, lib.raz_net_form.argtypes = N.SIGNATURES["raz_net_form"]
+    n = len(rows)
+    assert lib.raz_net_form(ctypes.byref(dn), n) == form
+    need = lib.raz_net_scratch_bytes(F, V, n)
+    scratch = np.zeros(max(need, 8), dtype=np.uint8)
+    pol = np.full((n + 1, 64), np.nan, np.float32)
+    val = np.full(n + 1, np.nan, np.float32)
+    assert lib.raz_net_forward(ctypes.byref(dn), own.ctypes.data, enemy.ctypes.data, None, pol.ctypes.data, val.ctypes.data, n,
+                               scratch.ctypes.data if need else None, need, None) == 0, lib.raz_last_error()
+    assert np.isnan(pol[n]).all() and np.isnan(val[n])
+    pol, val = pol[:n], val[:n]
+    if reserved == 4:
+        e = C.errors(pol, val, rp, rv)   # (the emulation fixes its own summation order in the matrix core: the stated 1e-5 here)
+        assert e[0] <= 1e-5, e
+    else:   # every row against the oracle, bit for bit: the contract itself (on 10 rows its error against f64 is too noisy a yardstick)
+        op, ov = _oracle(blob, own, enemy)
+        assert np.array_equal(pol.view(np.uint32), op.view(np.uint32)) and np.array_equal(val.view(np.uint32), ov.view(np.uint32))
+
