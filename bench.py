@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — MCTS self-play throughput of the batched engine on MI355X.  ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` on its own re-executes itself through torch.distributed.run with N ranks.)
 
@@ -23,9 +23,11 @@ long run holds at any instant; --tree-warm + W warm-up steps are run on that sta
 search trees that already hold a few dozen simulations.  metric = MCTS simulations/sec = start_search_my_move invocations / wall time, NN included,
 inputs resident in HBM, whole job over all GPUs.  games/hour is extrapolated from it (labelled).
 
-ONE line of at most 8 KB is printed (compact_line: the contract keys, `roofline`, `cpu_baseline`, one short object per leg with
-its value and its parity result); the full document with every leg's detail goes to bench_full.json (gpurun_out/ when present).
-At N = 1 the run also holds: the parity spot checks (8 sampled games of the 8192-game batch from the opening AND 8 sampled slots
+A plain run is the headline alone: set-up, warm-up, the K timed steps, the arrays of --dump-outputs and ONE line of at most 8 KB
+(compact_line: the contract keys and `roofline`).  Everything else it measures or checks runs only under --full, which adds
+`cpu_baseline` and one short object per leg with its value and its parity result to the line, and writes the full document with
+every leg's detail to --full-out (default: bench_full.json beside this file).
+At N = 1 a --full run also holds: the parity spot checks (8 sampled games of the 8192-game batch from the opening AND 8 sampled slots
 of the TIMED steady-state batch, root N / W bit for bit against the CPU oracle fed with the device net's outputs);
 `whole_games_measured` = the headline configuration (all 8192 slots) PLAYED for a fixed 120 s window with continuous batching -
 sims/s, games finished per hour, two games that finished inside the window == the oracle; `cpu_baseline` = the reference's own
@@ -34,13 +36,13 @@ the exact-f32 kernels; `ch5_yml_as_shipped` = the same batch with NO declared ov
 solver from turn 50) and the solver's measured share of a step; BASELINE configs[4] on one GPU; BASELINE configs[1] (4096 games x
 mini net x 200 sims/move, whole games, spot-checked) on the fused tree + net kernel the worker runs for 16-filter nets, at
 parallel_search_num 1 and mini.yml's 4, and on the two-kernel pipeline beside it; continuous batching; the bitboard-sweep HBM leg.
-At N > 1 (and at N = 1 under RAZ_BENCH_NCCL_WORLD1=1, an RCCL group of one rank): the record gather is timed and its payload
+In a --full run at N > 1 (and at N = 1 under RAZ_BENCH_NCCL_WORLD1=1, an RCCL group of one rank): the record gather is timed and its payload
 verified (per-rank checksums), and a small whole-game batch is played sharded AND on rank 0 alone: the gathered records must be
 byte-identical (SURVEY 8(d) Config 4's acceptance).
 `config1_mini_yml_as_shipped*`: mini.yml's play section with no declared override (thinking_loop 2, 4 simulations in flight, solver
 from turn 50) on both kernel forms - the solver-bound regime.
 
-`worker_end_to_end_config1`: BatchedSelfPlayWorker.run() itself for 60 s (files written, RCCL group of one rank).  The default run
+`worker_end_to_end_config1`: BatchedSelfPlayWorker.run() itself for 60 s (files written, RCCL group of one rank).  A --full run
 takes ~7 min on an MI355X box; --time-budget (600 s) keeps a slower box from delivering the line late: an extra leg whose nominal
 duration no longer fits is not started and says so.
 
@@ -473,18 +475,21 @@ def headline_leg(args, dev, rank, world, cdev, group=False):
     first_id = rank * args.games
     out = {}
 
-    # (1) untimed: the batch from the opening, 24 steps, then 8 sampled slots against the oracle
+    # (1) untimed: the batch from the opening, 24 steps, then (--full) 8 sampled slots against the oracle.  A plain run plays the
+    # 24 steps too: start() does not clear a slot's records beyond its current plies, so what these games record there is part of
+    # the records --dump-outputs writes, and those must not depend on --full
     spot = None
     if rank == 0 and not args.no_spotcheck:
         eng.start(first_id, args.sims)
         eng.step(24)
         eng.stats()
-        slots = [int(x) for x in np.linspace(0, args.games - 1, 8).astype(int)]
-        t0 = time.perf_counter()
-        checked = spotcheck_partial_search(eng, cfg, net, 0, first_id, slots)
-        spot = {"result": "ok", "what": f"{len(checked)} game ids sampled from the {args.games}-game batch after 24 steps from the opening: "
-                                        "root N (u32) and W (f64 bits) == the CPU oracle searching the same ids with the device net's outputs",
-                "games": checked, "seconds": time.perf_counter() - t0}
+        if args.full:
+            slots = [int(x) for x in np.linspace(0, args.games - 1, 8).astype(int)]
+            t0 = time.perf_counter()
+            checked = spotcheck_partial_search(eng, cfg, net, 0, first_id, slots)
+            spot = {"result": "ok", "what": f"{len(checked)} game ids sampled from the {args.games}-game batch after 24 steps from the opening: "
+                                            "root N (u32) and W (f64 bits) == the CPU oracle searching the same ids with the device net's outputs",
+                    "games": checked, "seconds": time.perf_counter() - t0}
 
     # (2) the steady state of continuous batching, W warm-up steps, K timed steps
     weights = None
@@ -514,7 +519,7 @@ def headline_leg(args, dev, rank, world, cdev, group=False):
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, timed_outputs(eng))
     net_check = None
-    if rank == 0 and not args.no_spotcheck and "f16x3" in (net.kernel_name or "") and not args.fused:
+    if rank == 0 and args.full and not args.no_spotcheck and "f16x3" in (net.kernel_name or "") and not args.fused:
         net_check = net_check_timed_leaves(eng, net, module, blob, dev)
     d = {k: float(st[k] - st0[k]) for k in ("total_sims", "nn_leaves", "selections")}
     served = float((c1["hits"] - c0["hits"]) + (c1["in_batch_duplicates"] - c0["in_batch_duplicates"]))
@@ -527,10 +532,10 @@ def headline_leg(args, dev, rank, world, cdev, group=False):
         elapsed = float(mx[3].item())
     total_sims, leaves, selections = (float(tot[i].item()) for i in range(3))
 
-    # (3) the single collective of the path: records -> rank 0, from HBM, cut to the games' plies
+    # (3) (--full) the single collective of the path: records -> rank 0, from HBM, cut to the games' plies
     t1 = time.perf_counter()
-    gather = {"collective": "none (1 GPU)", "bytes": 0}
-    if group:
+    gather = {"collective": "not run (--full runs it)" if group else "none (1 GPU)", "bytes": 0}
+    if group and args.full:
         import numpy as np
         from reversi_alpha_zero_amd.worker.self_play import gather_packed
         last = {}
@@ -559,7 +564,7 @@ def headline_leg(args, dev, rank, world, cdev, group=False):
     if rank != 0:
         return None
     spot_timed = None
-    if not args.no_spotcheck and not args.opening:
+    if args.full and not args.no_spotcheck and not args.opening:
         t2 = time.perf_counter()
         checked = spotcheck_steady_state(eng, cfg, net, 0, first_id, eng._staggered)
         spot_timed = {"result": "ok", "what": f"{len(checked)} slots of the TIMED steady-state batch (sampled across its plies), after the timed steps: root N (u32) "
@@ -1455,6 +1460,11 @@ def main():
     ap.add_argument("--no-spotcheck", action="store_true")
     ap.add_argument("--no-leaf-cache", action="store_true", help="headline engine without the cross-game evaluation cache")
     ap.add_argument("--fused", action="store_true", help="--net mini only: the headline leg on the fused tree + net kernel (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything else the benchmark measures or checks (~7 min on an MI355X box): the parity spot checks and "
+                         "net_check, the whole-game window, cpu_baseline and the extra legs at N = 1, the record gather and Config 4's "
+                         "acceptance at N > 1; and write the full document (--full-out).  --no-cpu-baseline, --no-extra-legs, "
+                         "--no-whole-games, --window-seconds, --legs and --time-budget shape such a run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="headline only (every other leg skipped)")
     ap.add_argument("--no-whole-games", action="store_true", help="skip the fixed-window leg on the headline configuration (~2.5 min)")
@@ -1462,9 +1472,9 @@ def main():
     ap.add_argument("--legs", default=None, help="comma-separated keys: run only these extra legs (e.g. ch5_yml_as_shipped,config1_4096x200_mini)")
     ap.add_argument("--time-budget", type=float, default=600.0,
                     help="seconds: an extra leg is not STARTED when the run's elapsed time plus the leg's nominal duration would pass this "
-                         "(the default run takes ~7 min on an MI355X box; on a slower box legs are dropped from the end, each with a note, "
+                         "(a --full run takes ~7 min on an MI355X box; on a slower box legs are dropped from the end, each with a note, "
                          "instead of the line arriving late or not at all)")
-    ap.add_argument("--full-out", default=None, help="where the full document goes (default: gpurun_out/bench_full.json if gpurun_out/ exists, else ./bench_full.json)")
+    ap.add_argument("--full-out", default=None, help="where the full document goes (default: bench_full.json beside bench.py)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the headline's last timed step computed as DIR/<name>.npy (rank 0; see timed_outputs)")
     args = ap.parse_args()
@@ -1485,7 +1495,7 @@ def main():
     # RAZ_BENCH_SHARED_GPU=1 (test rig only): several ranks share the visible GPUs and rendezvous over
     # gloo, to exercise the N > 1 code path on a 1-GPU box; the reported line says so.
     # RAZ_BENCH_NCCL_WORLD1=1 (test rig only): at N = 1, join an nccl (RCCL) group of ONE rank and run everything the N > 1 path runs
-    # on it - barriers, the all-reduces of the timed region, the record gather from HBM with its payload check.
+    # on it - barriers, the all-reduces of the timed region, and under --full the record gather from HBM with its payload check.
     shared_gpu = os.environ.get("RAZ_BENCH_SHARED_GPU") == "1"
     nccl_world1 = world == 1 and os.environ.get("RAZ_BENCH_NCCL_WORLD1") == "1"
     if shared_gpu:
@@ -1515,7 +1525,7 @@ def main():
     g.build()
 
     acceptance = None
-    if group and (not args.no_extra_legs or nccl_world1):
+    if group and args.full and (not args.no_extra_legs or nccl_world1):
         acceptance = config4_acceptance(dev, rank, world, cdev)
     res = headline_leg(args, dev, rank, world, cdev, group)
     if rank == 0:
@@ -1529,7 +1539,7 @@ def main():
             out["config"]["test_rig"] = "RAZ_BENCH_NCCL_WORLD1=1: the N > 1 code path (barriers, all-reduces, record gather) on an RCCL group of one rank"
         import gc
         checks = None
-        if world == 1 and not args.no_extra_legs and args.net == "ch5" and not args.no_whole_games:
+        if world == 1 and args.full and not args.no_extra_legs and args.net == "ch5" and not args.no_whole_games:
             gc.collect()
             torch.cuda.empty_cache()
             wg, recs = steady_window_leg(args, dev, blob, cfg, ply_weights, slots=args.games, seconds=args.window_seconds)
@@ -1542,7 +1552,7 @@ def main():
             out["headline_over_whole_games_sims_per_s"] = out["value"] / wg["value"]
             if not args.no_spotcheck and recs:
                 checks = start_complete_game_checks(dev, args, blob, cfg, recs)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the reference's own pure-Python self-play on this box's host cores, in this run (the game checks above keep two host
             # threads and an otherwise idle GPU busy meanwhile)
             ref = cpu_baseline_reference()
@@ -1561,7 +1571,7 @@ def main():
             out["whole_games_measured"]["parity_check_complete_games"] = join_complete_game_checks(
                 *checks, what="games of the window that were taken up late (ply >= 50) and finished inside it: every action, the winner and every ply's root N == "
                               "the game the CPU oracle plays for that id from the same position with the device net's outputs (800 sims/move)")
-        if world == 1 and not args.no_extra_legs:
+        if world == 1 and args.full and not args.no_extra_legs:
             legs = ((("headline_on_exact_f32_kernels", lambda: exact_f32_leg(args, dev, blob, cfg, ply_weights)),
                      ("ch5_yml_as_shipped", lambda: ch5_as_shipped_leg(args, dev, blob, ply_weights, games=args.games)))
                     if "f16x3" in out["dtype"] else ()) + (
@@ -1596,13 +1606,14 @@ def main():
                 except Exception as ex:   # never lose the main line over an extra leg
                     out[key] = {"error": repr(ex)}
         out["bench_wall_seconds"] = time.perf_counter() - T_MAIN
-        path = args.full_out or os.path.join(ROOT, "gpurun_out" if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else "", "bench_full.json")
-        try:
-            with open(path, "w") as f:
-                json.dump(out, f, indent=1)
-            out["_full_path"] = os.path.relpath(path, ROOT)
-        except OSError:
-            out["_full_path"] = None
+        if args.full:
+            path = args.full_out or os.path.join(ROOT, "bench_full.json")
+            try:
+                with open(path, "w") as f:
+                    json.dump(out, f, indent=1)
+                out["_full_path"] = os.path.relpath(path, ROOT)
+            except OSError:
+                out["_full_path"] = None
         print(json.dumps(compact_line(out)))
     if group:
         dist.destroy_process_group()

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=$PWD/gpurun_out/r4_s26; mkdir -p $O
 timeout 900 python -m pytest tests/test_oracle_solver.py tests/test_engine_gpu.py tests/test_engine_par_gpu.py -x -q -m gpu -k "solver or smallest_budget or evaluate_worker or shipped" > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -4 $O/pytest.log
-timeout 900 python bench.py --steps 5 --warmup 2 --no-whole-games --no-cpu-baseline --no-spotcheck --legs config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline --full-out $O/bench_full.json > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 5 --warmup 2 --no-whole-games --no-cpu-baseline --no-spotcheck --legs config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline --full-out $O/bench_full.json > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 python3 - <<PY
 import json
 d = json.load(open("$O/bench_full.json"))

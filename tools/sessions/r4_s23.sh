@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=$PWD/gpurun_out/r4_s29; mkdir -p $O
 RAZ_EXTRA_FLAGS="-DRAZ_SOLVER_NONEXACT_SCALAR=1" python reversi-alpha-zero_amd/build.py > $O/build_ab.log 2>&1; echo "build rc=$?"
-timeout 600 python bench.py --steps 5 --warmup 2 --no-whole-games --no-cpu-baseline --no-spotcheck --legs config1_mini_yml_as_shipped_two_kernel_pipeline,ch5_yml_as_shipped --full-out $O/bench_full_scalar_nonexact.json > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 5 --warmup 2 --no-whole-games --no-cpu-baseline --no-spotcheck --legs config1_mini_yml_as_shipped_two_kernel_pipeline,ch5_yml_as_shipped --full-out $O/bench_full_scalar_nonexact.json > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 python3 - <<PY
 import json
 d = json.load(open("$O/bench_full_scalar_nonexact.json"))

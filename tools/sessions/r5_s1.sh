@@ -11,7 +11,7 @@ python tools/smi_sampler.py --out $OUT/conv_power_smi_samples_7501.jsonl --hz 20
 cd /tmp && export TMPDIR=/tmp
 export RAZ_BENCH_MINI_SHIPPED=1
 P=$OUT/pmc_solver_bound; mkdir -p $P
-BENCH="python $ROOT/bench.py --net mini --games 4096 --sims 200 --steps 40 --warmup 5 --no-cpu-baseline --no-spotcheck --no-extra-legs --full-out $P/bench_full.json"
+BENCH="python $ROOT/bench.py --full --net mini --games 4096 --sims 200 --steps 40 --warmup 5 --no-cpu-baseline --no-spotcheck --no-extra-legs --full-out $P/bench_full.json"
 SETS=("" \
   "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_F32" \
   "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_VALU_MFMA_BUSY_CYCLES" \
@@ -30,5 +30,5 @@ for k, v in d.items():
         print(k, json.dumps(v))
 PY
 unset RAZ_BENCH_MINI_SHIPPED
-cd $ROOT && timeout 600 python bench.py --no-cpu-baseline --no-whole-games --no-spotcheck --steps 5 --warmup 2 --legs config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,config1_4096x200_mini --full-out $OUT/as_shipped_legs_full.json > $OUT/as_shipped_legs_line.json 2> $OUT/as_shipped_legs.err
+cd $ROOT && timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --no-spotcheck --steps 5 --warmup 2 --legs config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,config1_4096x200_mini --full-out $OUT/as_shipped_legs_full.json > $OUT/as_shipped_legs_line.json 2> $OUT/as_shipped_legs.err
 echo "legs rc=$?"; cut -c1-1500 $OUT/as_shipped_legs_line.json

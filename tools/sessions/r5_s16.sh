@@ -9,7 +9,7 @@ cd $ROOT
 LEGS=config1_4096x200_mini,config1_mini_yml_parallel_search_num_4
 for v in head cur it64 it256 cur2 head2; do
   case $v in cur*) unset RAZ_LIB_PATH;; head*) export RAZ_LIB_PATH=$ROOT/build/variants/libraz_head.so;; *) export RAZ_LIB_PATH=$ROOT/build/variants/libraz_$v.so;; esac
-  timeout 300 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_$v.json > /dev/null 2> $OUT/ab_$v.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_$v.json > /dev/null 2> $OUT/ab_$v.err
   python - <<PY
 import json
 d = json.load(open("$OUT/ab_$v.json"))

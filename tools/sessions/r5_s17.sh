@@ -9,7 +9,7 @@ LEGS=config1_4096x200_mini,config1_mini_yml_parallel_search_num_4
 for round in 1 2; do
 for v in head f0k0 f1k5 f2k6 f3k7 f1k4 f0k7; do
   export RAZ_LIB_PATH=$ROOT/build/variants/libraz_$v.so
-  timeout 300 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}_$round.json > /dev/null 2> $OUT/ab_${v}_$round.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}_$round.json > /dev/null 2> $OUT/ab_${v}_$round.err
   python - <<PY
 import json
 d = json.load(open("$OUT/ab_${v}_$round.json"))

@@ -8,7 +8,7 @@ cd $ROOT
 PROF_TIMEOUT=200 bash tools/run_profiles.sh headline 20 r5_s20/prof_headline "stats 3 4" > $OUT/prof_headline.log 2>&1; tail -2 $OUT/prof_headline.log
 timeout 200 python -m pytest tests/test_zz_fused_gpu.py tests/test_engine_gpu.py -q -m gpu -x -k "fused or solver_pool or suspended or with_solver_batch" > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $OUT/pytest.log
 LEGS=config1_4096x200_mini,config1_mini_yml_parallel_search_num_4,config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching
-timeout 400 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --legs $LEGS --full-out $OUT/legs_full.json > $OUT/legs_line.json 2> $OUT/legs.err; echo "legs rc=$?"
+timeout 400 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --legs $LEGS --full-out $OUT/legs_full.json > $OUT/legs_line.json 2> $OUT/legs.err; echo "legs rc=$?"
 python - <<PY
 import json
 d = json.load(open("$OUT/legs_full.json"))

@@ -5,7 +5,7 @@ OUT=$ROOT/gpurun_out/r5_s7; mkdir -p $OUT
 cd $ROOT
 timeout 1500 python -m pytest tests -q -m gpu -x > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.log
-timeout 900 python bench.py --no-cpu-baseline --no-whole-games --no-spotcheck --steps 5 --warmup 2 --legs config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,ch5_yml_as_shipped --full-out $OUT/as_shipped_legs_full.json > $OUT/as_shipped_legs_line.json 2> $OUT/as_shipped_legs.err
+timeout 900 python bench.py --full --no-cpu-baseline --no-whole-games --no-spotcheck --steps 5 --warmup 2 --legs config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,ch5_yml_as_shipped --full-out $OUT/as_shipped_legs_full.json > $OUT/as_shipped_legs_line.json 2> $OUT/as_shipped_legs.err
 echo "legs rc=$?"; tail -3 $OUT/as_shipped_legs.err
 python - <<PY
 import json

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/r5_s9; mkdir -p $OUT
 cd $ROOT
-timeout 1200 python bench.py --no-cpu-baseline --no-whole-games --steps 5 --warmup 2 --no-spotcheck --legs ${1:-config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching,worker_end_to_end_config1} --full-out $OUT/legs_full.json > $OUT/legs_line.json 2> $OUT/legs.err
+timeout 1200 python bench.py --full --no-cpu-baseline --no-whole-games --steps 5 --warmup 2 --no-spotcheck --legs ${1:-config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching,worker_end_to_end_config1} --full-out $OUT/legs_full.json > $OUT/legs_line.json 2> $OUT/legs.err
 echo "legs rc=$?"; tail -5 $OUT/legs.err
 python - <<PY
 import json

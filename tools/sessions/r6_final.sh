@@ -21,4 +21,4 @@ find $OUT -name "*kernel_stats.csv" | head
 find "$OUT" -name "*_kernel_trace.csv" -delete; find "$OUT" -name "*_counter_collection.csv" -delete
 timeout 100 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log | cut -c1-300
 timeout 1500 python -m pytest tests -q -m gpu -x > $OUT/pytest_gpu.log 2>&1; echo "pytest gpu rc=$?"; tail -3 $OUT/pytest_gpu.log
-timeout 1200 python bench.py --full-out $OUT/bench_r6_default_run_full.json > $OUT/bench_r6_default_run_line.json 2> $OUT/bench.err; echo "bench rc=$?"; wc -c $OUT/bench_r6_default_run_line.json; cut -c1-2500 $OUT/bench_r6_default_run_line.json
+timeout 1200 python bench.py --full --full-out $OUT/bench_r6_default_run_full.json > $OUT/bench_r6_default_run_line.json 2> $OUT/bench.err; echo "bench rc=$?"; wc -c $OUT/bench_r6_default_run_line.json; cut -c1-2500 $OUT/bench_r6_default_run_line.json

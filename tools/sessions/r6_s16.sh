@@ -10,7 +10,7 @@ LEGS=config1_4096x200_mini,config1_mini_yml_parallel_search_num_4,config1_mini_y
 for round in 1 2; do
 for v in old new fusedonly; do
   export RAZ_LIB_PATH=$ROOT/build/variants/libraz_$v.so
-  timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 20 --warmup 5 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}_$round.json > /dev/null 2> $OUT/ab_${v}_$round.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 20 --warmup 5 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}_$round.json > /dev/null 2> $OUT/ab_${v}_$round.err
   python - <<PY
 import json
 try:

@@ -7,7 +7,7 @@ cd $ROOT
 export RAZ_LIB_PATH=$ROOT/build/variants/libraz_gate1.so
 run() {  # name, legs, env...
   name=$1; legs=$2; shift 2
-  env "$@" timeout 400 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $legs --full-out $OUT/$name.json > /dev/null 2> $OUT/$name.err
+  env "$@" timeout 400 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $legs --full-out $OUT/$name.json > /dev/null 2> $OUT/$name.err
   python - <<PY
 import json
 try:

@@ -7,7 +7,7 @@ cd $ROOT
 LEGS=config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching
 for v in base slow8 slow32 memo6 memo8 ret1 ret3 base; do
   export RAZ_LIB_PATH=$ROOT/build/variants/libraz_$v.so
-  timeout 400 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}.json > /dev/null 2> $OUT/ab_${v}.err
+  timeout 400 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}.json > /dev/null 2> $OUT/ab_${v}.err
   python - <<PY
 import json
 try:

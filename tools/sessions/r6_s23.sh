@@ -7,7 +7,7 @@ LEGS=config1_mini_yml_as_shipped,config1_mini_yml_as_shipped_two_kernel_pipeline
 for v in inl1 inl2; do
 for b in 64 128; do
   export RAZ_LIB_PATH=$ROOT/build/variants/libraz_$v.so
-  RAZ_BENCH_SOLVER_BUDGET=$b timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}_$b.json > /dev/null 2> $OUT/ab_${v}_$b.err
+  RAZ_BENCH_SOLVER_BUDGET=$b timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/ab_${v}_$b.json > /dev/null 2> $OUT/ab_${v}_$b.err
   python - <<PY
 import json
 try:

@@ -7,7 +7,7 @@ cd $ROOT
 LEGS=config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching
 run() {
   name=$1; lib=$2; shift 2
-  env RAZ_LIB_PATH=$ROOT/build/variants/libraz_$lib.so "$@" timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/$name.json > /dev/null 2> $OUT/$name.err
+  env RAZ_LIB_PATH=$ROOT/build/variants/libraz_$lib.so "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/$name.json > /dev/null 2> $OUT/$name.err
   python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/r6_s26; mkdir -p $OUT
 cd $ROOT
 LEGS=config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching
 for n in 1 2 3 4 1; do
-  RAZ_BENCH_POOL_EVERY=$n timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/every_$n.json > /dev/null 2> $OUT/every_$n.err
+  RAZ_BENCH_POOL_EVERY=$n timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/every_$n.json > /dev/null 2> $OUT/every_$n.err
   python - <<PY
 import json
 try:

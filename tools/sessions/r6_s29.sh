@@ -5,7 +5,7 @@ OUT=$ROOT/gpurun_out/r6_s29; mkdir -p $OUT
 cd $ROOT
 LEGS=config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching
 for n in 0 2 4 0; do
-  RAZ_BENCH_PARTS=$n timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/parts_$n.json > /dev/null 2> $OUT/parts_$n.err
+  RAZ_BENCH_PARTS=$n timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/parts_$n.json > /dev/null 2> $OUT/parts_$n.err
   python - <<PY
 import json
 try:

@@ -7,7 +7,7 @@ cd $ROOT
 LEGS=config1_mini_yml_as_shipped_two_kernel_pipeline,config1_mini_yml_as_shipped_continuous_batching,config1_two_kernel_pipeline,config1_continuous_batching
 run() {
   name=$1; shift
-  env "$@" timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/$name.json > /dev/null 2> $OUT/$name.err
+  env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/$name.json > /dev/null 2> $OUT/$name.err
   python - <<PY
 import json
 try:

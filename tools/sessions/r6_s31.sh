@@ -5,7 +5,7 @@ OUT=$ROOT/gpurun_out/r6_s31; mkdir -p $OUT
 cd $ROOT
 LEGS=config1_mini_yml_as_shipped_continuous_batching,config1_mini_yml_as_shipped_two_kernel_pipeline
 for q in 6 12 16 8; do
-  GPU_MAX_HW_QUEUES=$q timeout 600 python bench.py --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/q$q.json > /dev/null 2> $OUT/q$q.err
+  GPU_MAX_HW_QUEUES=$q timeout 600 python bench.py --full --no-cpu-baseline --no-whole-games --steps 3 --warmup 1 --no-spotcheck --legs $LEGS --full-out $OUT/q$q.json > /dev/null 2> $OUT/q$q.err
   python - <<PY
 import json
 try:

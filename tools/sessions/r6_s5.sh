@@ -18,7 +18,7 @@ for line in open("$OUT/sweep_ab.jsonl"):
     r, l = d["roofline"], d["k_legal_moves"]
     print(d["mode"], "k_step %.3f ms %.0f GB/s frac %.3f | k_legal %.3f ms %.0f GB/s frac %.3f" % (r.get("avg_kernel_ms", 0), r["achieved"], r["frac"], l.get("avg_kernel_ms", 0), l["achieved"], l["frac"]))
 PY
-timeout 400 python bench.py --no-cpu-baseline --no-whole-games --legs worker_end_to_end_config1 --full-out $OUT/bench_worker_full.json > $OUT/bench_worker.json 2> $OUT/bench_worker.err; echo "bench worker rc=$?"
+timeout 400 python bench.py --full --no-cpu-baseline --no-whole-games --legs worker_end_to_end_config1 --full-out $OUT/bench_worker_full.json > $OUT/bench_worker.json 2> $OUT/bench_worker.err; echo "bench worker rc=$?"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench_worker_full.json"))

@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/r6_s6; mkdir -p $OUT
 cd $ROOT
 timeout 600 python -m pytest tests/test_continuous_gpu.py tests/test_worker_scale_gpu.py tests/test_multirank_gpu.py -q -m gpu -x > $OUT/pytest_worker.log 2>&1; echo "pytest worker rc=$?"; tail -3 $OUT/pytest_worker.log
-timeout 400 python bench.py --no-cpu-baseline --no-whole-games --legs worker_end_to_end_config1 --full-out $OUT/bench_worker_full.json > $OUT/bench_worker.json 2> $OUT/bench_worker.err; echo "bench worker rc=$?"
+timeout 400 python bench.py --full --no-cpu-baseline --no-whole-games --legs worker_end_to_end_config1 --full-out $OUT/bench_worker_full.json > $OUT/bench_worker.json 2> $OUT/bench_worker.err; echo "bench worker rc=$?"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench_worker_full.json"))

@@ -21,7 +21,7 @@ for line in open("$OUT/window_ab.jsonl"):
     print("window", d["window"], {k: d.get(k) for k in ("fused", "every", "continuous")}, "sims/s %.2f M" % (d["sims_per_s"] / 1e6), "steps", d.get("steps"), "rounds/answer", sp.get("pool_rounds_per_answer"), "busy lane-iterations", sp.get("busy_lane_iterations"), "util", sp.get("lane_utilisation"))
 PY
 tail -2 $OUT/ab.err | cut -c1-300
-timeout 400 python bench.py --no-cpu-baseline --no-whole-games --legs worker_end_to_end_config1 --full-out $OUT/bench_worker_full.json > $OUT/bench_worker.json 2> $OUT/bench_worker.err; echo "bench worker rc=$?"
+timeout 400 python bench.py --full --no-cpu-baseline --no-whole-games --legs worker_end_to_end_config1 --full-out $OUT/bench_worker_full.json > $OUT/bench_worker.json 2> $OUT/bench_worker.err; echo "bench worker rc=$?"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench_worker_full.json"))

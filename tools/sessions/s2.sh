@@ -5,7 +5,7 @@ O=gpurun_out/s2; mkdir -p $O
 python -c "import sys; sys.path.insert(0,'.'); import bench, reversi_alpha_zero_amd.engine, reversi_alpha_zero_amd.worker.self_play" || exit 9
 ( time timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1 ) 2> $O/pytest.time
 echo "pytest rc=$?"; tail -6 $O/pytest_gpu.log; cat $O/pytest.time
-( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time
+( time timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time
 echo "bench rc=$?"; tail -3 $O/bench.err; cat $O/bench.time
 timeout 600 bash tools/run_profiles.sh headline 20 s2/prof_headline "stats 3 4"
 tail -3 gpurun_out/s2/prof_headline/summary_pmc.txt

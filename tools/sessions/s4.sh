@@ -23,5 +23,5 @@ for name, games in (("prof_headline_full", 8192), ("prof_headline_1024", 1024)):
 else:
     print("no tree-kernel traffic profile")
 PY
-( time timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time
+( time timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time
 echo "bench rc=$?"; tail -3 $O/bench.err; cat $O/bench.time
