@@ -43,8 +43,8 @@ template <bool SOLVER>
 __global__ __launch_bounds__(64) RAZ_TREE_WAVES(SOLVER) void k_tree(raz_engine_dev E, uint32_t g0, uint32_t count) {
     if (blockIdx.x >= count) return;
     __shared__ float lds64[64];
-    __shared__ SolverLDS slds_store;
-    SolverLDS* slds_p = SOLVER ? &slds_store : nullptr;
+    __shared__ SolverLDS solver_lds;
+    SolverLDS* slds_p = SOLVER ? &solver_lds : nullptr;
     const uint32_t g = g0 + blockIdx.x;
     const int lane = threadIdx.x;
     if (g >= E.B) return;
@@ -52,62 +52,10 @@ __global__ __launch_bounds__(64) RAZ_TREE_WAVES(SOLVER) void k_tree(raz_engine_d
         if (lane == 0) E.nn_active[g] = 0;
         return;
     }
-    // ONE round trip: control block, path, the net's answer for the leaf of the previous launch
     uint32_t* gw = (uint32_t*)(E.game + g);
     Regs R;
-    R.cw = gw[lane];
-    path_load(E, R, (size_t)g, lane, true);
-    R.pol_raw = E.nn_policy[(size_t)g * 64 + lane];
-    R.val = E.nn_value[g];
-    R.nn = 0u;
-    R.path_dirty = 0u;
-    R.solve_pending = 0u;
-    path_load_rest(E, R, (size_t)g, lane);
-    {
-        const uint32_t phase = G32(R, GW(phase));
-        if (phase == RAZ_PHASE_DONE || phase == RAZ_PHASE_IDLE || G32(R, GW(error))) return;  // nn_active is already 0
-    }
-    if (RAZ_PROF_ON(E) && lane == 0) E.prof[(size_t)g * 8 + 5] += 1;
-    const int inner_max = ((E.cfg.reserved >> 12) & 0xf) ? (int)((E.cfg.reserved >> 12) & 0xf) : kInnerMax;
-    const raz_engine_dev& E0 = E;
-    for (int it = 0; it < inner_max; ++it) {
-        const raz_engine_dev& E = fresh_descriptor<RAZ_FRESH_DESC>(E0);
-        uint32_t phase = G32(R, GW(phase));
-        if (phase == RAZ_PHASE_DONE || phase == RAZ_PHASE_IDLE) break;
-        if (G32(R, GW(error))) break;
-        // a descent suspended at an in-simulation solve (select_leaf) goes on where it stands, before anything else
-        const bool suspended = SOLVER && G32(R, GW(leaf_kind)) == RAZ_LEAF_SOLVE_PENDING;
-        unsigned long long t0 = prof_now();
-        if (!suspended) {
-            if (G32(R, GW(leaf_kind)) != RAZ_LEAF_NONE) backup_leaf<false>(E, R, g, G32(R, GW(player)) - 1, lane, lds64);
-            prof_add(E, g, 0, t0, lane);
-            t0 = prof_now();
-            // controller: loop because a decided move may immediately need another decision
-            // (turn-0 bypass) before a search with simulations starts
-            for (int guard = 0; guard < 8; ++guard) {
-                phase = G32(R, GW(phase));
-                if (phase == RAZ_PHASE_NEW_MOVE) {
-                    if (R.solve_pending) break;   // the root's end-game solve ran out of this launch's budget: it goes on at the next launch
-                    begin_move<SOLVER>(E, R, g, lane, slds_p);
-                    continue;
-                }
-                if (phase == RAZ_PHASE_SEARCH && (int32_t)G32(R, GW(sims_left)) <= 0) {
-                    decide_move(E, R, g, lane);
-                    continue;
-                }
-                break;
-            }
-            prof_add(E, g, 1, t0, lane);
-            phase = G32(R, GW(phase));
-            if (phase != RAZ_PHASE_SEARCH || (int32_t)G32(R, GW(sims_left)) <= 0 || G32(R, GW(error))) break;
-            t0 = prof_now();
-        }
-        select_leaf<SOLVER, false>(E, R, g, lane, slds_p, g, suspended ? G32(R, GW(leaf_node)) : G32(R, GW(root_node)),
-                                   suspended ? (int)G32(R, GW(depth)) : 0, false, suspended ? (int)G32(R, GW(leaf_action)) - 1 : -1);
-        prof_add(E, g, 2, t0, lane);
-        const uint32_t lk = G32(R, GW(leaf_kind));
-        if (lk != RAZ_LEAF_TERMINAL && lk != RAZ_LEAF_SOLVED) break;  // needs the net (or, suspended at a solve, the next launch)
-    }
+    if (!load_game<kProfRuntime>(E, R, gw, g, lane)) return;  // nn_active is already 0
+    tree_steps<SOLVER, kProfRuntime>(E, R, g, lane, lds64, slds_p, inner_budget(E), nullptr);
     // write the game back: one coalesced store (+ the path when a descent ran)
     gw[lane] = R.cw;
     if (R.path_dirty) path_store(E, R, (size_t)g, lane);
@@ -115,32 +63,13 @@ __global__ __launch_bounds__(64) RAZ_TREE_WAVES(SOLVER) void k_tree(raz_engine_d
 }
 
 // ------------------------------------------------------------------ parallel_search_num > 1: k_tree_par
-// The reference runs simulation_num_per_move coroutines under asyncio.Semaphore(parallel_search_num)
-// beside a prediction_worker that turns the queued leaves into one api.predict call
-// (agent/player.py:189-215, 329-355).  raz-sched-v1 (oracle/orc_mcts.c search_moves)
-// is that event loop in exact virtual time; one ROUND of it is
-//   B   the batch came back: the simulations waiting for the net finish their expansion and return up
-//       their paths, in the order their leaves were queued;
-//   C   freed semaphore slots are taken by the next simulations, each running until it blocks;
-//   D   the simulations sleeping on now_expanding whose key was expanded in B go on, in sleep order;
-//   C'  slots freed in D are refilled.
-// A game keeps parallel_search_num simulation SLOTS (block = raz_game layout, only the leaf_* / depth
-// lanes meaningful; path and leaf-exchange rows indexed g * K + slot); lane j of three VGPRs holds
-// slot j's state, order number and node slept on.  One launch = at most one round; a fill that runs
-// out of its per-launch budget (games whose simulations all end on finished positions would otherwise
-// be the launch's stragglers) continues at the next launch WITHOUT an intervening B, so the result
-// does not depend on the budget.
-// The kernel is ONE loop with a single call site each for the controller, the descent and the return
-// path (the three large inlined bodies): duplicating them per phase doubled the code to 66 KB, more
-// than the instruction cache two CUs share.  Each iteration picks the next operation of the round -
-// resume the oldest queued leaf (B), start a simulation in a free slot (C, C'), wake the next sleeper
-// (D) - then runs at most one slot load, one descent, one return.
+// One launch = at most one round of raz-sched-v1 (par_round, raz_engine_core.h); the round's leaves go to the net batch.
 template <bool SOLVER>
 __global__ __launch_bounds__(64) RAZ_TREE_WAVES(SOLVER) void k_tree_par(raz_engine_dev E, uint32_t g0, uint32_t count) {
     if (blockIdx.x >= count) return;
     __shared__ float lds64[64];
-    __shared__ SolverLDS slds_store;
-    SolverLDS* slds_p = SOLVER ? &slds_store : nullptr;
+    __shared__ SolverLDS solver_lds;
+    SolverLDS* slds_p = SOLVER ? &solver_lds : nullptr;
     const uint32_t g = g0 + blockIdx.x;
     const int lane = threadIdx.x;
     if (g >= E.B) return;
@@ -149,155 +78,12 @@ __global__ __launch_bounds__(64) RAZ_TREE_WAVES(SOLVER) void k_tree_par(raz_engi
         if (lane < (int)K) E.nn_active[(size_t)g * K + lane] = 0;
         return;
     }
-    const unsigned long long kmask = (1ULL << K) - 1ULL;  // K <= 16
     uint32_t* gw = (uint32_t*)(E.game + g);
     Regs R;
-    R.cw = gw[lane];
-    R.pnode = R.pmirror = R.pact = 0u;
-    R.pol_raw = 0.0f;
-    R.val = 0.0f;
-    R.nn = 0u;
-    R.path_dirty = 0u;
-    R.solve_pending = 0u;
     Slots T;
-    T.st = T.sq = T.pk = 0u;
-    uint32_t* myblk = E.sim + ((size_t)g * K + (uint32_t)(lane < (int)K ? lane : 0)) * 64;
-    if (lane < (int)K) {
-        T.st = myblk[GW(sim_state)];
-        T.sq = myblk[GW(sim_seq)];
-        T.pk = myblk[GW(sim_parked)];
-    }
-    uint32_t nnmask = 0u;
-    {
-        const uint32_t phase = G32(R, GW(phase));
-        if (phase == RAZ_PHASE_DONE || phase == RAZ_PHASE_IDLE || G32(R, GW(error))) {
-            if (lane < (int)K) E.nn_active[(size_t)g * K + lane] = 0;
-            return;
-        }
-    }
-    if (RAZ_PROF_ON(E) && lane == 0) E.prof[(size_t)g * 8 + 5] += 1;
-    int budget = (int)K + (((E.cfg.reserved >> 12) & 0xf) ? (int)((E.cfg.reserved >> 12) & 0xf) : kInnerMax);
-    constexpr uint32_t kStageB = 0u, kStageC = 1u, kStageC2 = 2u, kStageD = 4u;  // D outlives a launch only under a suspended solve
-    uint32_t stage = G32(R, GW(par_stage));
-    unsigned long long dmask = stage == kStageD ? (unsigned long long)G32(R, GW(par_dmask)) : 0ULL;  // sleepers still to poll in D
-    const raz_engine_dev& E0 = E;
-    for (;;) {
-        const raz_engine_dev& E = fresh_descriptor<RAZ_FRESH_DESC>(E0);
-        if (G32(R, GW(error))) break;
-        // ---- the next operation of the round
-        int j = -1;
-        bool resume = false, wake = false, suspended = false;
-        const unsigned long long solving = SOLVER ? (__ballot(T.st == RAZ_SIM_SOLVING) & kmask) : 0ULL;
-        if (solving) {  // a descent suspended at an in-simulation solve goes on first: it was a start (C / C') or a wake (D)
-            j = __ffsll((long long)solving) - 1;
-            suspended = true;
-            wake = stage == kStageD;
-        } else if (stage == kStageB) {
-            const unsigned long long m = __ballot(T.st == RAZ_SIM_WAIT_NET) & kmask;
-            if (!m) {
-                stage = kStageC;
-                continue;
-            }
-            j = pick_min_seq(T.sq, m);
-            resume = true;
-        } else if (stage == kStageD) {
-            if (!dmask) {
-                stage = kStageC2;
-                continue;
-            }
-            j = pick_min_seq(T.sq, dmask);
-            dmask &= ~(1ULL << j);
-            wake = true;
-        } else {  // C / C': the per-move controller, then a new simulation into a free slot
-            for (int guard = 0; guard < 8; ++guard) {
-                const uint32_t phase = G32(R, GW(phase));
-                if (phase == RAZ_PHASE_NEW_MOVE) {
-                    if (R.solve_pending) break;   // the root's end-game solve ran out of this launch's budget: it goes on at the next launch
-                    begin_move<SOLVER>(E, R, g, lane, slds_p);
-                    continue;
-                }
-                if (phase == RAZ_PHASE_SEARCH && (int32_t)G32(R, GW(sims_left)) <= 0) {  // every simulation has returned
-                    decide_move(E, R, g, lane);
-                    continue;
-                }
-                break;
-            }
-            const unsigned long long busy = __ballot(T.st != RAZ_SIM_FREE) & kmask;
-            const int inflight = __popcll(busy);
-            const int to_start = (int32_t)G32(R, GW(sims_left)) - inflight;
-            if (G32(R, GW(phase)) != RAZ_PHASE_SEARCH || G32(R, GW(error)) || inflight >= (int)K || to_start <= 0) {
-                if (stage == kStageC2) {
-                    stage = kStageB;  // the round is complete: the next launch starts with B
-                    break;
-                }
-                // D: sleepers whose key is still in now_expanding sleep on (their nodes' tags are read in one go)
-                const uint32_t pl = G32(R, GW(player)) - 1;
-                const bool sl = lane < (int)K && T.st == RAZ_SIM_WAIT_EXPAND;
-                uint32_t tg = 0u;
-                if (sl) tg = node_hdr(node_ptr(E, g, T.pk))->tag;
-                dmask = __ballot(sl && !((tg >> (6 + pl)) & 1u)) & kmask;
-                stage = kStageD;
-                continue;
-            }
-            if (budget <= 0) break;  // the fill goes on at the next launch, without a B in between
-            --budget;
-            j = __ffsll((long long)(~busy & kmask)) - 1;
-        }
-        // ---- at most one slot load, one descent, one return
-        bool back = resume;
-        if (resume || wake || suspended) slot_load(E, R, g, (uint32_t)j, lane, resume);
-        if (!resume) {
-            const unsigned long long t0 = prof_now();
-            select_leaf<SOLVER, true>(E, R, g, lane, slds_p, g * K + (uint32_t)j,
-                                      suspended ? G32(R, GW(leaf_node)) : (wake ? lane_u32(T.pk, j) : G32(R, GW(root_node))),
-                                      (wake || suspended) ? (int)G32(R, GW(depth)) : 0, wake && !suspended,
-                                      suspended ? (int)G32(R, GW(leaf_action)) - 1 : -1);
-            prof_add(E, g, 2, t0, lane);
-            const uint32_t kind = G32(R, GW(leaf_kind));
-            if (SOLVER && kind == RAZ_LEAF_SOLVE_PENDING) {  // out of solver budget: the slot keeps the descent, the launch is over for the game
-                T.st = writelane_r(T.st, RAZ_SIM_SOLVING, j, lane);
-                slot_store(E, R, g, (uint32_t)j, lane);
-                S32(R, GW(leaf_kind), RAZ_LEAF_NONE);
-                break;
-            }
-            if (kind == RAZ_LEAF_TERMINAL || kind == RAZ_LEAF_SOLVED) {
-                back = true;  // ended on a finished game / a solved position: returns up its path at once
-            } else if (kind == RAZ_LEAF_EXPAND || kind == RAZ_LEAF_PARKED) {
-                if (kind == RAZ_LEAF_EXPAND || !wake) {  // a sleeper that goes back to sleep keeps its place
-                    const uint32_t seq = G32(R, GW(par_seq_next));
-                    S32(R, GW(par_seq_next), seq + 1);
-                    T.sq = writelane_r(T.sq, seq, j, lane);
-                }
-                if (kind == RAZ_LEAF_EXPAND) {
-                    T.st = writelane_r(T.st, RAZ_SIM_WAIT_NET, j, lane);
-                    nnmask |= 1u << j;
-                } else {
-                    T.st = writelane_r(T.st, RAZ_SIM_WAIT_EXPAND, j, lane);
-                    T.pk = writelane_r(T.pk, G32(R, GW(sim_parked)), j, lane);
-                }
-                slot_store(E, R, g, (uint32_t)j, lane);
-                S32(R, GW(leaf_kind), RAZ_LEAF_NONE);
-            }
-        }
-        if (back) {
-            const unsigned long long t0 = prof_now();
-            backup_leaf<true>(E, R, g, G32(R, GW(player)) - 1, lane, lds64);
-            T.st = writelane_r(T.st, RAZ_SIM_FREE, j, lane);
-            prof_add(E, g, 0, t0, lane);
-        }
-    }
-    if (SOLVER && R.solve_pending && stage == kStageD) {
-        S32(R, GW(par_dmask), (uint32_t)dmask);
-        S32(R, GW(par_stage), kStageD);
-    } else
-        S32(R, GW(par_stage), stage == kStageD ? kStageC2 : stage);
-    gw[lane] = R.cw;
-    if (lane < (int)K) {
-        myblk[GW(sim_state)] = T.st;
-        myblk[GW(sim_seq)] = T.sq;
-        myblk[GW(sim_parked)] = T.pk;
-        E.nn_active[(size_t)g * K + lane] = (uint8_t)((nnmask >> lane) & 1u);
-    }
+    if (!load_game_and_slots<kProfRuntime>(E, R, T, gw, g, K, lane)) return;
+    const uint32_t nnmask = par_round<SOLVER, kProfRuntime, false>(E, R, T, g, K, lane, lds64, slds_p);
+    write_back_game_and_slots<SOLVER>(E, R, T, gw, g, K, lane, nnmask);
 }
 
 // Reduce the per-game statistics into counters[0..6] (one block).  Per-game words instead of

@@ -1,10 +1,12 @@
 // raz_engine_core.h — the per-game device code of the engine (one wavefront per game, lane = board square): wave helpers,
 // tree storage, the control block in registers, PUCT, the end-game solver, backup, the per-move controller and the descent.
-// Included by raz_engine.hip (k_tree, k_tree_par and the rest of the engine) and by raz_engine_fused.hip (k_tree_net): two
-// translation units, so that adding the fused kernel leaves the code generated for the others untouched.
+// Included by raz_engine.hip (k_tree, k_tree_par and the rest of the engine) and by raz_engine_fused.hip (k_tree_net, k_tree_par_net):
+// two translation units, so that the fused kernels leave the code generated for the others untouched.  The four tree kernels share
+// their bodies, at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "raz_bitboard.h"
 #include "raz_detmath.h"
 #include "raz_engine.h"
@@ -15,6 +17,11 @@ namespace {
 constexpr int kInnerMax = 2;  // max simulations completed per game per launch (terminal leaves need no net);
                               // larger values make the few games with runs of terminal leaves stragglers
                               // that set the launch's duration (8: 58.6M sims/s, 2: 62.2M on the bench config)
+// kInnerMax, or raz_engine_config.reserved bits 12-15 when they are set
+__device__ __forceinline__ int inner_budget(const raz_engine_dev& E) {
+    const int n = (int)((E.cfg.reserved >> 12) & 0xf);
+    return n ? n : kInnerMax;
+}
 
 // ------------------------------------------------------------------ wave helpers
 // Lanes of the game's wave communicate through HBM (lane 0 writes game state, all lanes read it).
@@ -209,6 +216,10 @@ __device__ __forceinline__ unsigned long long prof_now() { return __builtin_amdg
 __device__ __forceinline__ void prof_add(const raz_engine_dev& E, uint32_t g, int k, unsigned long long t0, int lane) {
     if (RAZ_PROF_ON(E) && lane == 0) E.prof[(size_t)g * 8 + k] += prof_now() - t0;
 }
+// The timing hooks of the tree kernels' shared bodies (PROF, end of this file).  kProfRuntime (k_tree: phases 0 / 1 / 2, k_tree_par: 0 / 2):
+// the clock is read in every launch, the ticks are kept when the profile is on.  kProfFused (k_tree_net in a -DRAZ_FUSED_PROF
+// measurement build, tools/fused_phase_profile.py: 0 / 1 / 2, and 5 for the in-wave forward): every hook ends one phase and starts the next.
+enum { kProfNone, kProfRuntime, kProfFused };
 
 // ------------------------------------------------------------------ tree storage
 __device__ __forceinline__ uint32_t key_hash(raz_bb b, raz_bb w, uint32_t tagkey) {
@@ -291,25 +302,37 @@ __device__ __forceinline__ void node_read_squares(unsigned char* p, int L, raz_b
     Ni = on ? node_N(p, L)[rk] : 0u;
 }
 
-// The engine's descriptor (raz_engine_dev: ~90 scalar registers of pointers and configuration words) as a kernel ARGUMENT is loaded once
-// at the kernel's entry and then lives in scalar registers for the whole launch - more than a wave has, so the compiler parks them in the
-// lanes of spare vector registers (v_writelane / v_readlane: vector-ALU work in an issue-bound kernel).  Handing the step loop the
-// kernel-argument segment's address through an empty asm once per step makes every use a scalar load from the (cached) segment
-// where it is needed instead.  k_tree_net / k_tree_par_net: bit 3 of RAZ_FRESH_1 / RAZ_FRESH_K; k_tree / k_tree_par: RAZ_FRESH_DESC.
-#ifndef RAZ_FRESH_DESC
-#define RAZ_FRESH_DESC 1
-#endif
-template <int ON>
+// Two ways of keeping loop-invariant values out of the registers of the tree kernels' step loops (the shared bodies at the end of this
+// file), each a fixed choice measured with configs[1] whole games, A/B on one box:
+//  * fresh_descriptor, all four kernels: the engine's descriptor (raz_engine_dev: ~90 scalar registers of pointers and configuration
+//    words) as a kernel ARGUMENT is loaded once at the kernel's entry and then lives in scalar registers for the whole launch - more than
+//    a wave has, so the compiler parks them in the lanes of spare vector registers (v_writelane / v_readlane: vector-ALU work in an
+//    issue-bound kernel).  Handing the loop the kernel-argument segment's address through an empty asm once per step (k_tree_par: per
+//    round operation) makes every use a scalar load from the (cached) segment where it is needed instead.  k_tree_net<false> 206 -> 121
+//    spilled scalar registers, 31 -> 21 spilled vector registers, 3985 -> 3670 vector instructions, 105.3-105.8 -> 107.0-107.4 M sims/s;
+//    k_tree_par_net<false> 256 -> 193 and 4547 -> 4020, 96.8 -> 98.7-99.0 M; mini.yml as shipped 21.6 -> 22.0-22.2 M
+//    (profiles/r6/fused_kernels_descriptor_from_the_kernarg_segment_ab.json).
+//  * fresh_lane, k_tree_par_net only (per step, per round operation, per queued leaf): the lane id through an empty asm, so that the
+//    lane's addresses and masks are recomputed where they are used instead of being spilled around the in-wave net call: 56 spilled
+//    VGPRs -> 0, 92.3 -> 96.3 M sims/s.  k_tree_net made spill-free the same way (30 -> 0) runs 105.3 -> 101.3 M (lane id alone -2.5 %):
+//    it is bound by instruction issue, 4 waves x 21 % per SIMD, and its spills - one batch of scratch stores before the forward, one of
+//    loads behind it - cost less than the recomputation (profiles/r5/fused_kernel_ab.json).
+// Both are right only inside a kernel: the bodies that use them are force-inlined.
 __device__ __forceinline__ const raz_engine_dev& fresh_descriptor(const raz_engine_dev& E) {
 #ifndef RAZ_WAVE_EMU
-    if (ON) {
-        typedef const raz_engine_dev __attribute__((address_space(4))) * kernarg_ptr;
-        kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();   // (the descriptor is the kernels' FIRST argument)
-        asm volatile("" : "+s"(p));
-        return *(const raz_engine_dev*)p;
-    }
-#endif
+    typedef const raz_engine_dev __attribute__((address_space(4))) * kernarg_ptr;
+    kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();   // (the descriptor is the kernels' FIRST argument)
+    asm volatile("" : "+s"(p));
+    return *(const raz_engine_dev*)p;
+#else
     return E;
+#endif
+}
+__device__ __forceinline__ int fresh_lane(int lane) {
+#ifndef RAZ_WAVE_EMU
+    asm volatile("" : "+v"(lane));
+#endif
+    return lane;
 }
 
 // ------------------------------------------------------------------ the game's control block in registers
@@ -1131,6 +1154,25 @@ __device__ void begin_move(const raz_engine_dev& E, Regs& R, uint32_t g, int lan
     wave_sync();
 }
 
+// The controller of every tree kernel: a loop, because a decided move may immediately need another decision (turn-0 bypass) before a
+// search with simulations starts.
+template <bool SOLVER>
+__device__ __forceinline__ void run_controller(const raz_engine_dev& E, Regs& R, uint32_t g, int lane, SolverLDS* S) {
+    for (int guard = 0; guard < 8; ++guard) {
+        const uint32_t phase = G32(R, GW(phase));
+        if (phase == RAZ_PHASE_NEW_MOVE) {
+            if (R.solve_pending) break;   // the root's end-game solve ran out of this launch's budget: it goes on at the next launch
+            begin_move<SOLVER>(E, R, g, lane, S);
+            continue;
+        }
+        if (phase == RAZ_PHASE_SEARCH && (int32_t)G32(R, GW(sims_left)) <= 0) {  // every simulation has returned
+            decide_move(E, R, g, lane);
+            continue;
+        }
+        break;
+    }
+}
+
 // ------------------------------------------------------------------ descent to the next leaf
 // PAR (k_tree_par): the descent may start at the node a sleeping simulation stood on (start_node /
 // start_depth, `polling`: the solver look of :237-251 lies behind it), every edge taken gets its virtual
@@ -1399,8 +1441,12 @@ constexpr unsigned long long kSimLanes =
 #undef LB
 
 struct Slots {
-    uint32_t st, sq, pk;  // lane j = slot j: RAZ_SIM_*, order number, node slept on
+    uint32_t st, sq, pk;       // lane j = slot j: RAZ_SIM_*, order number, node slept on
+    unsigned long long kmask;  // the K slots
+    uint32_t stage;            // of the round (par_round)
+    unsigned long long dmask;  // stage D: the sleepers still to poll
 };
+constexpr uint32_t kStageB = 0u, kStageC = 1u, kStageC2 = 2u, kStageD = 4u;
 
 __device__ __forceinline__ void slot_load(const raz_engine_dev& E, Regs& R, uint32_t g, uint32_t j, int lane, bool with_net) {
     const size_t gi = (size_t)g * E.K + j;
@@ -1431,6 +1477,243 @@ __device__ __forceinline__ int pick_min_seq(uint32_t sq, unsigned long long mask
         }
     }
     return best;
+}
+
+// ------------------------------------------------------------------ the tree kernels' shared bodies
+// The loading of a game, the simulation steps of k_tree / k_tree_net and one raz-sched-v1 round of k_tree_par / k_tree_par_net, written
+// once for the classic kernels (raz_engine.hip) and the fused ones (raz_engine_fused.hip).  Force-inlined: fresh_descriptor is right
+// only inside a kernel, and each kernel keeps ONE call site of each large body (select_leaf, backup_leaf, the controller) - the slot
+// kernels are 42 KB / 71 KB (<false> / <true>) against the instruction cache two CUs share.  PROF: the timing hooks (kProf* above).
+
+// The game's control block, the path in flight and the net's answer for the leaf of the previous launch: ONE round trip.  false: the
+// game has nothing to do.
+template <int PROF>
+__device__ __forceinline__ bool load_game(const raz_engine_dev& E, Regs& R, const uint32_t* gw, uint32_t g, int lane) {
+    R.cw = gw[lane];
+    path_load(E, R, (size_t)g, lane, true);
+    R.pol_raw = E.nn_policy[(size_t)g * 64 + lane];
+    R.val = E.nn_value[g];
+    R.nn = 0u;
+    R.path_dirty = 0u;
+    R.solve_pending = 0u;
+    path_load_rest(E, R, (size_t)g, lane);
+    const uint32_t phase = G32(R, GW(phase));
+    if (phase == RAZ_PHASE_DONE || phase == RAZ_PHASE_IDLE || G32(R, GW(error))) return false;
+    if (PROF == kProfRuntime && RAZ_PROF_ON(E) && lane == 0) E.prof[(size_t)g * 8 + 5] += 1;
+    return true;
+}
+
+// Up to n simulation steps, each: back up the previous leaf, run the per-move controller, descend to the next leaf.  They go on while
+// the leaves need no net (TERMINAL, SOLVED) and - k_tree_net - after every EXPAND, which eval(t0) evaluates in the wave; eval ==
+// nullptr (k_tree): an EXPAND leaf goes to the net batch.  t0: the clock of the phase the last hook started.
+template <bool SOLVER, int PROF, class N, class Eval>
+__device__ __forceinline__ void tree_steps(const raz_engine_dev& E0, Regs& R, uint32_t g, int lane, float* lds64, SolverLDS* slds_p, N n,
+                                           Eval eval) {
+    for (N it = 0; it < n; ++it) {
+        const raz_engine_dev& E = fresh_descriptor(E0);
+        uint32_t phase = G32(R, GW(phase));
+        if (phase == RAZ_PHASE_DONE || phase == RAZ_PHASE_IDLE) break;
+        if (G32(R, GW(error))) break;
+        // a descent suspended at an in-simulation solve (select_leaf) goes on where it stands, before anything else
+        const bool suspended = SOLVER && G32(R, GW(leaf_kind)) == RAZ_LEAF_SOLVE_PENDING;
+        unsigned long long t0 = PROF ? prof_now() : 0ULL;
+        if (!suspended) {
+            if (G32(R, GW(leaf_kind)) != RAZ_LEAF_NONE) backup_leaf<false>(E, R, g, G32(R, GW(player)) - 1, lane, lds64);
+            if (PROF) {
+                prof_add(E, g, 0, t0, lane);
+                t0 = prof_now();
+            }
+            run_controller<SOLVER>(E, R, g, lane, slds_p);
+            if (PROF) prof_add(E, g, 1, t0, lane);
+            if (PROF == kProfFused) t0 = prof_now();
+            phase = G32(R, GW(phase));
+            if (phase != RAZ_PHASE_SEARCH || (int32_t)G32(R, GW(sims_left)) <= 0 || G32(R, GW(error))) break;
+            if (PROF == kProfRuntime) t0 = prof_now();
+        }
+        select_leaf<SOLVER, false>(E, R, g, lane, slds_p, g, suspended ? G32(R, GW(leaf_node)) : G32(R, GW(root_node)),
+                                   suspended ? (int)G32(R, GW(depth)) : 0, false, suspended ? (int)G32(R, GW(leaf_action)) - 1 : -1);
+        if (PROF) prof_add(E, g, 2, t0, lane);
+        if (PROF == kProfFused) t0 = prof_now();
+        const uint32_t lk = G32(R, GW(leaf_kind));
+        if constexpr (!std::is_same<Eval, decltype(nullptr)>::value) {
+            if (lk == RAZ_LEAF_EXPAND) {
+                eval(t0);
+                continue;
+            }
+        }
+        if (lk != RAZ_LEAF_TERMINAL && lk != RAZ_LEAF_SOLVED) break;  // needs the net (or, suspended at a solve, the next launch)
+    }
+}
+
+// parallel_search_num > 1: the control block, the simulation slots' states and the round's stage (block = raz_game layout, only the
+// leaf_* / depth lanes meaningful; path and leaf-exchange rows indexed g * K + slot).  false: the game has nothing to do (its slots'
+// nn_active flags are cleared).
+template <int PROF>
+__device__ __forceinline__ bool load_game_and_slots(const raz_engine_dev& E, Regs& R, Slots& T, const uint32_t* gw, uint32_t g, uint32_t K,
+                                                    int lane) {
+    T.kmask = (1ULL << K) - 1ULL;  // K <= 16
+    R.cw = gw[lane];
+    R.pnode = R.pmirror = R.pact = 0u;
+    R.pol_raw = 0.0f;
+    R.val = 0.0f;
+    R.nn = 0u;
+    R.path_dirty = 0u;
+    R.solve_pending = 0u;
+    T.st = T.sq = T.pk = 0u;
+    const uint32_t* myblk = E.sim + ((size_t)g * K + (uint32_t)(lane < (int)K ? lane : 0)) * 64;
+    if (lane < (int)K) {
+        T.st = myblk[GW(sim_state)];
+        T.sq = myblk[GW(sim_seq)];
+        T.pk = myblk[GW(sim_parked)];
+    }
+    const uint32_t phase = G32(R, GW(phase));
+    if (phase == RAZ_PHASE_DONE || phase == RAZ_PHASE_IDLE || G32(R, GW(error))) {
+        if (lane < (int)K) E.nn_active[(size_t)g * K + lane] = 0;
+        return false;
+    }
+    if (PROF == kProfRuntime && RAZ_PROF_ON(E) && lane == 0) E.prof[(size_t)g * 8 + 5] += 1;
+    T.stage = G32(R, GW(par_stage));
+    T.dmask = T.stage == kStageD ? (unsigned long long)G32(R, GW(par_dmask)) : 0ULL;
+    return true;
+}
+// ... and back: stage D outlives a launch only under a suspended solve (the sleepers still to poll are kept with it)
+template <bool SOLVER>
+__device__ __forceinline__ void write_back_game_and_slots(const raz_engine_dev& E, Regs& R, const Slots& T, uint32_t* gw, uint32_t g,
+                                                          uint32_t K, int lane, uint32_t nnmask) {
+    if (SOLVER && R.solve_pending && T.stage == kStageD) {
+        S32(R, GW(par_dmask), (uint32_t)T.dmask);
+        S32(R, GW(par_stage), kStageD);
+    } else
+        S32(R, GW(par_stage), T.stage == kStageD ? kStageC2 : T.stage);
+    gw[lane] = R.cw;
+    uint32_t* myblk = E.sim + ((size_t)g * K + (uint32_t)(lane < (int)K ? lane : 0)) * 64;
+    if (lane < (int)K) {
+        myblk[GW(sim_state)] = T.st;
+        myblk[GW(sim_seq)] = T.sq;
+        myblk[GW(sim_parked)] = T.pk;
+        E.nn_active[(size_t)g * K + lane] = (uint8_t)((nnmask >> lane) & 1u);
+    }
+}
+
+// One ROUND of raz-sched-v1.  The reference runs simulation_num_per_move coroutines under asyncio.Semaphore(parallel_search_num) beside a
+// prediction_worker that turns the queued leaves into one api.predict call (agent/player.py:189-215, 329-355); raz-sched-v1 (DESIGN.md
+// §5; oracle/orc_mcts.c search_moves) is that event loop in exact virtual time, and one round of it is
+//   B   the batch came back: the simulations waiting for the net finish their expansion and return up their paths, in the order their
+//       leaves were queued;
+//   C   freed semaphore slots are taken by the next simulations, each running until it blocks;
+//   D   the simulations sleeping on now_expanding whose key was expanded in B go on, in sleep order;
+//   C'  slots freed in D are refilled.
+// A game keeps parallel_search_num = K simulation SLOTS; lane j of T.st / T.sq / T.pk holds slot j's state, order number and node
+// slept on.  The body is ONE loop with a single call site each for the controller, the descent and the return path (the three large
+// inlined bodies): duplicating them per stage doubled the code to 66 KB, more than the instruction cache two CUs share.  Each iteration
+// picks the next operation of the round - resume the oldest queued leaf (B), start a simulation in a free slot (C, C'), wake the next
+// sleeper (D) - then runs at most one slot load, one descent, one return.  Returns the slots whose leaves were queued for the net, when
+// the round is complete (T.stage B again), when the fill has run out of its budget (games whose simulations all end on finished
+// positions would otherwise be the launch's stragglers: the next call continues it WITHOUT an intervening B, so the result does not
+// depend on the budget) or when a solve waits for the solver pool (R.solve_pending).
+// NET (k_tree_par_net): the caller refreshes the descriptor once per round, the lane id is refreshed per operation; otherwise
+// (k_tree_par) the descriptor is refreshed per operation.
+template <bool SOLVER, int PROF, bool NET>
+__device__ __forceinline__ uint32_t par_round(const raz_engine_dev& E0, Regs& R, Slots& T, uint32_t g, uint32_t K, int lane0, float* lds64,
+                                              SolverLDS* slds_p) {
+    const unsigned long long kmask = T.kmask;
+    uint32_t nnmask = 0u;
+    int budget = (int)K + inner_budget(E0);
+    for (;;) {
+        const int lane = NET ? fresh_lane(lane0) : lane0;
+        const raz_engine_dev& E = NET ? E0 : fresh_descriptor(E0);
+        if (G32(R, GW(error))) break;
+        // ---- the next operation of the round
+        int j = -1;
+        bool resume = false, wake = false, suspended = false;
+        const unsigned long long solving = SOLVER ? (__ballot(T.st == RAZ_SIM_SOLVING) & kmask) : 0ULL;
+        if (solving) {  // a descent suspended at an in-simulation solve goes on first: it was a start (C / C') or a wake (D)
+            j = __ffsll((long long)solving) - 1;
+            suspended = true;
+            wake = T.stage == kStageD;
+        } else if (T.stage == kStageB) {
+            const unsigned long long m = __ballot(T.st == RAZ_SIM_WAIT_NET) & kmask;
+            if (!m) {
+                T.stage = kStageC;
+                continue;
+            }
+            j = pick_min_seq(T.sq, m);
+            resume = true;
+        } else if (T.stage == kStageD) {
+            if (!T.dmask) {
+                T.stage = kStageC2;
+                continue;
+            }
+            j = pick_min_seq(T.sq, T.dmask);
+            T.dmask &= ~(1ULL << j);
+            wake = true;
+        } else {  // C / C': the per-move controller, then a new simulation into a free slot
+            run_controller<SOLVER>(E, R, g, lane, slds_p);
+            const unsigned long long busy = __ballot(T.st != RAZ_SIM_FREE) & kmask;
+            const int inflight = __popcll(busy);
+            const int to_start = (int32_t)G32(R, GW(sims_left)) - inflight;
+            if (G32(R, GW(phase)) != RAZ_PHASE_SEARCH || G32(R, GW(error)) || inflight >= (int)K || to_start <= 0) {
+                if (T.stage == kStageC2) {
+                    T.stage = kStageB;  // the round is complete: the next one starts with B
+                    break;
+                }
+                // D: sleepers whose key is still in now_expanding sleep on (their nodes' tags are read in one go)
+                const uint32_t pl = G32(R, GW(player)) - 1;
+                const bool sl = lane < (int)K && T.st == RAZ_SIM_WAIT_EXPAND;
+                uint32_t tg = 0u;
+                if (sl) tg = node_hdr(node_ptr(E, g, T.pk))->tag;
+                T.dmask = __ballot(sl && !((tg >> (6 + pl)) & 1u)) & kmask;
+                T.stage = kStageD;
+                continue;
+            }
+            if (budget <= 0) break;  // the fill goes on at the next call, without a B in between
+            --budget;
+            j = __ffsll((long long)(~busy & kmask)) - 1;
+        }
+        // ---- at most one slot load, one descent, one return
+        bool back = resume;
+        if (resume || wake || suspended) slot_load(E, R, g, (uint32_t)j, lane, resume);
+        if (!resume) {
+            const unsigned long long t0 = PROF ? prof_now() : 0ULL;
+            select_leaf<SOLVER, true>(E, R, g, lane, slds_p, g * K + (uint32_t)j,
+                                      suspended ? G32(R, GW(leaf_node)) : (wake ? lane_u32(T.pk, j) : G32(R, GW(root_node))),
+                                      (wake || suspended) ? (int)G32(R, GW(depth)) : 0, wake && !suspended,
+                                      suspended ? (int)G32(R, GW(leaf_action)) - 1 : -1);
+            if (PROF) prof_add(E, g, 2, t0, lane);
+            const uint32_t kind = G32(R, GW(leaf_kind));
+            if (SOLVER && kind == RAZ_LEAF_SOLVE_PENDING) {  // out of solver budget: the slot keeps the descent, the launch is over for the game
+                T.st = writelane_r(T.st, RAZ_SIM_SOLVING, j, lane);
+                slot_store(E, R, g, (uint32_t)j, lane);
+                S32(R, GW(leaf_kind), RAZ_LEAF_NONE);
+                break;
+            }
+            if (kind == RAZ_LEAF_TERMINAL || kind == RAZ_LEAF_SOLVED) {
+                back = true;  // ended on a finished game / a solved position: returns up its path at once
+            } else if (kind == RAZ_LEAF_EXPAND || kind == RAZ_LEAF_PARKED) {
+                if (kind == RAZ_LEAF_EXPAND || !wake) {  // a sleeper that goes back to sleep keeps its place
+                    const uint32_t seq = G32(R, GW(par_seq_next));
+                    S32(R, GW(par_seq_next), seq + 1);
+                    T.sq = writelane_r(T.sq, seq, j, lane);
+                }
+                if (kind == RAZ_LEAF_EXPAND) {
+                    T.st = writelane_r(T.st, RAZ_SIM_WAIT_NET, j, lane);
+                    nnmask |= 1u << j;
+                } else {
+                    T.st = writelane_r(T.st, RAZ_SIM_WAIT_EXPAND, j, lane);
+                    T.pk = writelane_r(T.pk, G32(R, GW(sim_parked)), j, lane);
+                }
+                slot_store(E, R, g, (uint32_t)j, lane);
+                S32(R, GW(leaf_kind), RAZ_LEAF_NONE);
+            }
+        }
+        if (back) {
+            const unsigned long long t0 = PROF ? prof_now() : 0ULL;
+            backup_leaf<true>(E, R, g, G32(R, GW(player)) - 1, lane, lds64);
+            T.st = writelane_r(T.st, RAZ_SIM_FREE, j, lane);
+            if (PROF) prof_add(E, g, 0, t0, lane);
+        }
+    }
+    return nnmask;
 }
 
 }  // namespace
