@@ -396,6 +396,45 @@ int raz_engine_solver_stats(raz_engine* e, uint64_t* out15, raz_stream_t stream)
  * 3 the games' control blocks, 6 the solver blocks, 7 / 8 / 9 the solver pool's lane state / headers / active list) copied to host
  * memory.  RAZ_EINVAL when offset + bytes reaches beyond the array.  Synchronises the device. */
 int raz_engine_debug_read(raz_engine* e, int which, size_t offset, size_t bytes, void* host_out);
+/* Diagnostics: the device forms of raz-math-v1 / raz-rng-v1 (csrc/raz_detmath.h) and of the wave-level reductions of the tree
+ * kernels (csrc/raz_engine_core.h) applied to n elements / rows - the very functions the tree kernels call, so that a test can
+ * compare them with the oracle and with numpy on inputs no game reaches.  All buffers are DEVICE buffers, rows are 64 wide
+ * (lane = column); asynchronous on `stream`.  what, in0, in1 (NULL where "-") -> out:
+ *   PHILOX           u32[n][6] c0..c3,k0,k1                    -                  u32[n][4]
+ *   RNG_PAIR         u32[n][6] seed,game,purpose,event,sub,idx -                  f64[n][2]
+ *   LOG, EXP, COS2   f64[n]                                    -                  f64[n]
+ *   POW              f64[n] x                                  f64[n] y           f64[n]
+ *   EXPF, TANHF      f32[n]                                    -                  f32[n]
+ *   GAMMA_HALF_PAIR  u32[n][4] seed,game,event,m               -                  f64[n][2]
+ *   GAMMA_ATTEMPT    f64[n] alpha                              u32[n][5] seed,game,event,sub,t   f64[n][2] X, accepted (0.0 / 1.0)
+ *   NP_SUM_F32       f32[n][64]                                -                  f32[n]
+ *   ARGMAX_F64, ARGMAX_NONNEG_F64   f64[n][64]                 -                  i32[n]   (NONNEG: finite values >= +0 only)
+ *   MAX_F64          f64[n][64]                                -                  f64[n]
+ *   SUM_U32          u32[n][64]                                -                  u32[n]
+ *   ROOT_GAMMAS      f64[n] alpha                              u32[n][4] k,seed,game,event
+ *                    -> f64[n][64] Gamma samples by rank, then f64[n][64] the normalised noise, then u32[n] rounds of the rejection
+ *                    loop (0 at alpha = 0.5), one after the other in `out` ((1024 + 4) n bytes); a row whose k is outside 1..64 or
+ *                    whose alpha is not a finite number > 0 is answered with zeros
+ *   CHOICE           f64[n][64] policy                         f64[n] uniform     i32[n]
+ * RAZ_EINVAL for an unknown selector, a missing buffer or n >= 2^24 rows of a 64-wide selector. */
+#define RAZ_PROBE_PHILOX 0
+#define RAZ_PROBE_RNG_PAIR 1
+#define RAZ_PROBE_LOG 2
+#define RAZ_PROBE_EXP 3
+#define RAZ_PROBE_COS2 4
+#define RAZ_PROBE_POW 5
+#define RAZ_PROBE_EXPF 6
+#define RAZ_PROBE_TANHF 7
+#define RAZ_PROBE_GAMMA_HALF_PAIR 8
+#define RAZ_PROBE_GAMMA_ATTEMPT 9
+#define RAZ_PROBE_NP_SUM_F32 10
+#define RAZ_PROBE_ARGMAX_F64 11
+#define RAZ_PROBE_ARGMAX_NONNEG_F64 12
+#define RAZ_PROBE_MAX_F64 13
+#define RAZ_PROBE_SUM_U32 14
+#define RAZ_PROBE_ROOT_GAMMAS 15
+#define RAZ_PROBE_CHOICE 16
+int raz_spec_probe(int what, const void* in0, const void* in1, void* out, size_t n, raz_stream_t stream);
 /* config.play.resign_threshold is mutated while the worker runs (worker/self_play.py:250-260: +-0.01 per 100
  * no-resign test games); moves decided from the next raz_engine_step on use the new value.  Trees, records and
  * random streams are untouched. */

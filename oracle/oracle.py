@@ -180,6 +180,11 @@ def _load_ext_locked():
         lib.orc_dirichlet_gammas.restype = None
         lib.orc_gamma_sample.argtypes = [c_double] + [c_uint32] * 4
         lib.orc_gamma_sample.restype = c_double
+        lib.orc_gamma_sample_t.argtypes = [c_double] + [c_uint32] * 4 + [POINTER(c_uint32)]
+        lib.orc_gamma_sample_t.restype = c_double
+        lib.orc_spec_map.argtypes = [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t]
+        lib.orc_gamma_sample_t_n.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t]
+        lib.orc_gamma_sample_t_n.restype = None
         lib.orc_dirichlet_noise_of_mask.argtypes = [c_uint64, c_double, c_uint32, c_uint32, c_uint32, POINTER(c_double * 64)]
         lib.orc_dirichlet_noise_of_mask.restype = None
         lib.orc_net_forward_planes.argtypes = [c_char_p, c_size_t, c_void_p, c_void_p, c_void_p]

@@ -161,8 +161,11 @@ float orc_det_tanhf(float x) {
  * (no shipped config needs it - config.py:138 dirichlet_alpha = 0.5 - but lib/bitboard.py:162-171 takes any alpha). */
 double orc_det_cos2(double u);
 
-double orc_gamma_sample(double alpha, uint32_t seed, uint32_t game, uint32_t event, uint32_t sub) {
+/* The sample and, in *t_accepted (nullable), the index of the attempt that produced it: attempts are independent Philox blocks, the
+ * sample is the accepted one with the smallest t (the device evaluates several per round, csrc/raz_engine_core.h root_noise). */
+double orc_gamma_sample_t(double alpha, uint32_t seed, uint32_t game, uint32_t event, uint32_t sub, uint32_t* t_accepted) {
     double d[2];
+    if (t_accepted) *t_accepted = 0;
     if (alpha == 1.0) {
         orc_rng_pair(seed, game, 2, event, sub, 0, d);
         return -orc_det_log(1.0 - d[0]);
@@ -186,8 +189,10 @@ double orc_gamma_sample(double alpha, uint32_t seed, uint32_t game, uint32_t eve
             if (V <= 0.0) continue;
             V = (V * V) * V;
             const double U = 1.0 - e[1];
-            if (U < 1.0 - 0.0331 * (z2 * z2)) return b * V;
-            if (orc_det_log(U) < 0.5 * z2 + b * ((1.0 - V) + orc_det_log(V))) return b * V;
+            if (U < 1.0 - 0.0331 * (z2 * z2) || orc_det_log(U) < 0.5 * z2 + b * ((1.0 - V) + orc_det_log(V))) {
+                if (t_accepted) *t_accepted = t;
+                return b * V;
+            }
         }
     }
     for (uint32_t t = 0;; ++t) {
@@ -195,13 +200,23 @@ double orc_gamma_sample(double alpha, uint32_t seed, uint32_t game, uint32_t eve
         double U = d[0], V = -orc_det_log(1.0 - d[1]);
         if (U <= 1.0 - alpha) {
             double X = orc_det_pow(U, 1.0 / alpha);
-            if (X <= V) return X;
+            if (X <= V) {
+                if (t_accepted) *t_accepted = t;
+                return X;
+            }
         } else {
             double Y = -orc_det_log((1.0 - U) / alpha);
             double X = orc_det_pow(1.0 - alpha + alpha * Y, 1.0 / alpha);
-            if (X <= V + Y) return X;
+            if (X <= V + Y) {
+                if (t_accepted) *t_accepted = t;
+                return X;
+            }
         }
     }
+}
+
+double orc_gamma_sample(double alpha, uint32_t seed, uint32_t game, uint32_t event, uint32_t sub) {
+    return orc_gamma_sample_t(alpha, seed, game, event, sub, NULL);
 }
 
 /* cos^2(2 pi u), u in [0,1): exact octant reduction + 9-term Taylor sine on [0, pi/4] (Estrin). */
@@ -253,4 +268,34 @@ void orc_dirichlet_noise_of_mask(u64 mask, double alpha, uint32_t seed, uint32_t
     for (int j = 0; j < k; ++j) acc += g[j];
     k = 0;
     for (int i = 0; i < 64; ++i) out[i] = (mask >> i & 1) ? g[k++] / acc : 0.0;
+}
+
+/* ---- batch forms for the tests that compare the device with this file element by element (tests/spec_cases.py):
+ * the element-wise selectors of raz_spec_probe (include/raz.h RAZ_PROBE_*, same numbers, same buffer layouts) on host arrays. */
+int orc_spec_map(int what, const void* in0, const void* in1, void* out, size_t n) {
+    const uint32_t* u0 = (const uint32_t*)in0;
+    const double* d0 = (const double*)in0;
+    const double* d1 = (const double*)in1;
+    const float* f0 = (const float*)in0;
+    double* od = (double*)out;
+    for (size_t i = 0; i < n; ++i) {
+        switch (what) {
+            case 0: orc_philox4x32_10(u0 + 6 * i, u0 + 6 * i + 4, (uint32_t*)out + 4 * i); break;
+            case 1: orc_rng_pair(u0[6 * i], u0[6 * i + 1], u0[6 * i + 2], u0[6 * i + 3], u0[6 * i + 4], u0[6 * i + 5], od + 2 * i); break;
+            case 2: od[i] = orc_det_log(d0[i]); break;
+            case 3: od[i] = orc_det_exp(d0[i]); break;
+            case 4: od[i] = orc_det_cos2(d0[i]); break;
+            case 5: od[i] = orc_det_pow(d0[i], d1[i]); break;
+            case 6: ((float*)out)[i] = orc_det_expf(f0[i]); break;
+            case 7: ((float*)out)[i] = orc_det_tanhf(f0[i]); break;
+            default: return -1;
+        }
+    }
+    return 0;
+}
+
+/* orc_gamma_sample_t over n (alpha, (seed, game, event, sub)) tuples. */
+void orc_gamma_sample_t_n(const double* alpha, const uint32_t* key4, double* x, uint32_t* t_accepted, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        x[i] = orc_gamma_sample_t(alpha[i], key4[4 * i], key4[4 * i + 1], key4[4 * i + 2], key4[4 * i + 3], t_accepted + i);
 }

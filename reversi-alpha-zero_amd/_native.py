@@ -132,6 +132,7 @@ SIGNATURES.update({
     "raz_engine_solver_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
     "raz_engine_debug_read": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
     "raz_engine_set_resign_threshold": (c_int, [c_void_p, c_int, ctypes.c_double]),
+    "raz_spec_probe": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -470,6 +470,66 @@ __device__ __forceinline__ void env_step(Env& e, int action) {
     e.legal = r.legal;
 }
 
+// The root's Dirichlet noise (lib/bitboard.py:162-171), wave-wide: lane j < k ends with `gam` = the Gamma(alpha) sample of the j-th
+// legal move and `noise` = gam / sum of the k samples (added in ascending order); the other lanes with 0.  `rounds`: passes of
+// the rejection loop (0 on the alpha = 0.5 pair path), counted only where COUNT_ROUNDS asks for it: csrc/raz_spec_probe.hip, which
+// runs this very function under test.  (alpha and seed by reference: the tree kernels then read the two config fields where they
+// always did, instead of holding them in SGPRs across the loop - the form that leaves their register allocation as it was.)
+template <bool COUNT_ROUNDS = false>
+__device__ __forceinline__ void root_noise(const double& alpha, const uint32_t& seed, uint32_t game_id, uint32_t ev, int k, int lane,
+                                           double& gam, double& noise, uint32_t& rounds) {
+    const uint32_t bit = lane < k ? 1u : 0u;
+    rounds = 0;
+    gam = 0.0;   // Gamma(alpha) sample j belongs to the j-th legal move = lane j
+    if (alpha == 0.5) {
+        // Box-Muller pairs: lane m < ceil(k/2) turns one Philox block into the two Gamma(1/2)
+        // variates of legal moves 2m and 2m+1 (no rejection, no divergence).
+        double g0 = 0.0, g1 = 0.0;
+        if (2 * lane < k) raz_gamma_half_pair(seed, game_id, ev, (uint32_t)lane, g0, g1);
+        const double s0 = __shfl(g0, lane >> 1), s1 = __shfl(g1, lane >> 1);
+        if (bit) gam = (lane & 1) ? s1 : s0;
+    } else {
+        // Attempts of the rejection sampler are independent Philox blocks, so lane l evaluates attempt t = l / k of
+        // sample j = l % k (up to 8 attempts per sample per round) and each legal move takes its sample's first
+        // accepted attempt: one evaluation deep instead of the slowest lane's rejection count.
+        int A = 64 / k;
+        if (A > 8) A = 8;
+        int myt = 0;
+#pragma unroll
+        for (int i = 1; i < 8; ++i) myt += (lane >= i * k) ? 1 : 0;
+        const int myj = lane - myt * k;
+        bool need = bit != 0;
+        for (uint32_t round = 0;; ++round) {
+            double X = 0.0;
+            bool ok = false;
+            if (lane < A * k) ok = raz_gamma_attempt(alpha, seed, game_id, ev, (uint32_t)myj, round * (uint32_t)A + (uint32_t)myt, X);
+            const unsigned long long am = __ballot(ok);
+            int src = -1;
+            if (need) {
+                for (int t = 0; t < A; ++t) {
+                    const int l = lane + k * t;
+                    if ((am >> l) & 1ULL) {
+                        src = l;
+                        break;
+                    }
+                }
+            }
+            const double got = __shfl(X, src < 0 ? lane : src);
+            if (src >= 0) {
+                gam = got;
+                need = false;
+            }
+            if (__ballot(need) == 0ULL) {
+                if (COUNT_ROUNDS) rounds = round + 1;
+                break;
+            }
+        }
+    }
+    double acc = 0.0;
+    for (int j = 0; j < k; ++j) acc += lane_f64(gam, j);
+    noise = bit ? gam / acc : 0.0;
+}
+
 // ------------------------------------------------------------------ select (agent/player.py:395-428)
 // RANK space: lane r < k holds the statistics of the node's r-th legal move in ascending square order (the node's
 // arrays as they lie in memory), the other lanes hold zeros.  The reference masks by the legal moves (`* legal`), so
@@ -490,51 +550,9 @@ __device__ int select_action(const raz_engine_dev& E, Regs& R, uint32_t g, doubl
     if (is_root && c.noise_eps > 0.0) {  // (1-eps) p + eps Dir(alpha), fresh at every root visit (:415-417)
         const unsigned long long tp = prof_now();
         const uint32_t ev = G32(R, GW(ev_dirichlet));
-        double gam = 0.0;   // Gamma(alpha) sample j belongs to the j-th legal move = lane j
-        if (c.dirichlet_alpha == 0.5) {
-            // Box-Muller pairs: lane m < ceil(k/2) turns one Philox block into the two Gamma(1/2)
-            // variates of legal moves 2m and 2m+1 (no rejection, no divergence).
-            double g0 = 0.0, g1 = 0.0;
-            if (2 * lane < k) raz_gamma_half_pair(c.seed, game_id, ev, (uint32_t)lane, g0, g1);
-            const double s0 = __shfl(g0, lane >> 1), s1 = __shfl(g1, lane >> 1);
-            if (bit) gam = (lane & 1) ? s1 : s0;
-        } else {
-            // Attempts of the rejection sampler are independent Philox blocks, so lane l evaluates attempt t = l / k of
-            // sample j = l % k (up to 8 attempts per sample per round) and each legal move takes its sample's first
-            // accepted attempt: one evaluation deep instead of the slowest lane's rejection count.
-            int A = 64 / k;
-            if (A > 8) A = 8;
-            int myt = 0;
-#pragma unroll
-            for (int i = 1; i < 8; ++i) myt += (lane >= i * k) ? 1 : 0;
-            const int myj = lane - myt * k;
-            bool need = bit != 0;
-            for (uint32_t round = 0;; ++round) {
-                double X = 0.0;
-                bool ok = false;
-                if (lane < A * k) ok = raz_gamma_attempt(c.dirichlet_alpha, c.seed, game_id, ev, (uint32_t)myj, round * (uint32_t)A + (uint32_t)myt, X);
-                const unsigned long long am = __ballot(ok);
-                int src = -1;
-                if (need) {
-                    for (int t = 0; t < A; ++t) {
-                        const int l = lane + k * t;
-                        if ((am >> l) & 1ULL) {
-                            src = l;
-                            break;
-                        }
-                    }
-                }
-                const double got = __shfl(X, src < 0 ? lane : src);
-                if (src >= 0) {
-                    gam = got;
-                    need = false;
-                }
-                if (__ballot(need) == 0ULL) break;
-            }
-        }
-        double acc = 0.0;
-        for (int j = 0; j < k; ++j) acc += lane_f64(gam, j);
-        const double noise = bit ? gam / acc : 0.0;
+        double gam, noise;
+        uint32_t rounds;
+        root_noise(c.dirichlet_alpha, c.seed, game_id, ev, k, lane, gam, noise, rounds);
         const float keep = (float)(1.0 - c.noise_eps);
         const double p64 = (double)(keep * p32) + c.noise_eps * noise;
         u = (c.c_puct * p64) * xx / (1.0 + Nd);
@@ -1016,6 +1034,23 @@ __device__ void finalize_move(const raz_engine_dev& E, Regs& R, uint32_t g, int 
     S32(R, GW(phase), G32(R, GW(one_move)) ? RAZ_PHASE_IDLE : (r.status ? RAZ_PHASE_DONE : RAZ_PHASE_NEW_MOVE));
 }
 
+// np.random.choice(range(64), p=policy) on the uniform d0 (agent/player.py:112): cdf = cumsum(policy); cdf /= cdf[-1];
+// searchsorted(cdf, d0, side="right") = the number of squares whose cdf <= d0, at most 63.  Wave-uniform.  d0 = uniform() is drawn
+// between the cumsum and the comparison (a callable, so that the controller's instruction order is what it was before this was a function).
+template <class U>
+__device__ __forceinline__ int choice_of(double policy, U uniform, int lane) {
+    double acc = 0.0, cdf = 0.0;
+    for (int i = 0; i < 64; ++i) {
+        acc += lane_f64(policy, i);
+        if (i == lane) cdf = acc;
+    }
+    cdf = cdf / acc;
+    const double d0 = uniform();
+    int action = __popcll(__ballot(cdf <= d0));
+    if (action > 63) action = 63;
+    return action;
+}
+
 // ------------------------------------------------------------------ per-move controller
 // action_with_evaluation (:82-134) after a search (or the turn-0 bypass) has finished, then
 // SelfPlayWorker.start_game's env.step (worker/self_play.py:155-162).  Returns with the game either
@@ -1048,17 +1083,12 @@ __device__ void decide_move(const raz_engine_dev& E, Regs& R, uint32_t g, int la
     else
         policy = (lane == amax_n) ? 1.0 : 0.0;
     // np.random.choice(range(64), p=policy) (:112): cdf = cumsum; cdf /= cdf[-1]; searchsorted right
-    double acc = 0.0, cdf = 0.0;
-    for (int i = 0; i < 64; ++i) {
-        acc += lane_f64(policy, i);
-        if (i == lane) cdf = acc;
-    }
-    cdf = cdf / acc;
     const uint32_t ev = G32(R, GW(ev_choice));
-    double d0, d1;
-    raz_rng_pair(c.seed, game_id, RAZ_RNG_CHOICE, ev, 0, 0, d0, d1);
-    int action = __popcll(__ballot(cdf <= d0));
-    if (action > 63) action = 63;
+    const int action = choice_of(policy, [&]() {
+        double d0, d1;
+        raz_rng_pair(c.seed, game_id, RAZ_RNG_CHOICE, ev, 0, 0, d0, d1);
+        return d0;
+    }, lane);
     S32(R, GW(ev_choice), ev + 1);
     // re-thinking rule (:113-118)
     const int abv = wave_argmax_f64(q + (Ni > 0 ? 100.0 : 0.0), lane);

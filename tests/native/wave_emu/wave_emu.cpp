@@ -124,12 +124,14 @@ uint64_t ballot(bool pred, const char* what, int line) {
     Fiber* f = running;
     const int k = (int)(f->ops & 1u);
     f->pub[k] = pred ? 1u : 0u;
-    ++f->ops;
+    const auto op = ++f->ops;
     arrive(waves[f->wave], what, line);
     uint64_t m = 0;
     const int base = f->wave * 64;
+    // the lanes that took part in THIS operation: those that have issued at least as many as the caller (every live lane of a wave meets at
+    // every operation, so their counts agree) - among them lanes that have since run to their end, which a slower lane must still count
     for (int i = 0; i < 64 && base + i < n_fibers; ++i)
-        if (!fibers[base + i].done && fibers[base + i].pub[k]) m |= 1ULL << i;
+        if (fibers[base + i].ops >= op && fibers[base + i].pub[k]) m |= 1ULL << i;
     return m;
 }
 

@@ -277,3 +277,150 @@ def test_virtual_time_schedule_is_representative_of_the_real_event_loop():
         st[loop] = pvr.stats(games, 24)
     for k in ("leaves/sim", "top share", "entropy"):
         assert abs(st["real"][k] - st["virtual"][k]) <= 0.2 * abs(st["virtual"][k]), (k, st)
+
+
+# ---- raz-math-v1 against mathematics, raz-rng-v1's samplers against their distributions -------------------------------------------
+def measure_det_math(n_random=20000):
+    """Worst error of every raz-math-v1 function of the oracle over the structured lists of tests/spec_cases.py (random blocks thinned to
+    n_random) against mpmath at 200 bits: {name: (error, argument)}.  Units: log, exp - ulps of the true value; cos2, tanhf - absolute;
+    pow, expf - relative; cos2_pair - |cos2(u) + cos2(u + 1/4 mod 1) - 1|."""
+    import mpmath as mp
+    import spec_cases as S
+    lib = O.load_ext()
+    mp.mp.prec = 200
+
+    def ulp_of(v):   # of the float64 binade the true value lies in
+        m, e = mp.frexp(abs(v))
+        return mp.ldexp(1, max(int(e) - 53, -1074))
+
+    def worst(errs, args):
+        i = int(np.argmax([float(e) for e in errs]))
+        return float(errs[i]), float(args[i])
+
+    out = {}
+    x = S.log_cases(n_random, 4096)
+    x = x[(x > 0) & np.isfinite(x)]
+    y = S.orc_map(lib, S.LOG, x, None, np.float64)
+    errs = []
+    for a, b in zip(x.tolist(), y.tolist()):
+        t = mp.log(mp.mpf(a))
+        errs.append(abs(mp.mpf(b) - t) / ulp_of(t) if t != 0 else mp.mpf(0 if b == 0.0 else 1e9))
+    out["log"] = worst(errs, x)
+    x = S.exp_cases(n_random)
+    x = x[(x >= -745.0) & (x <= 709.78)]
+    y = S.orc_map(lib, S.EXP, x, None, np.float64)
+    errs = []
+    for a, b in zip(x.tolist(), y.tolist()):
+        t = mp.exp(mp.mpf(a))
+        errs.append(abs(mp.mpf(b) - t) / ulp_of(t))
+    out["exp"] = worst(errs, x)
+    x = S.cos2_cases(n_random)
+    y = S.orc_map(lib, S.COS2, x, None, np.float64)
+    errs = [abs(mp.mpf(b) - mp.cos(2 * mp.pi * mp.mpf(a)) ** 2) for a, b in zip(x.tolist(), y.tolist())]
+    out["cos2"] = worst(errs, x)
+    x4 = x + 0.25
+    x4 = np.where(x4 >= 1.0, x4 - 1.0, x4)
+    exact = (x4 - 0.25 == x) | (x4 + 0.75 == x)                             # u + 1/4 representable: every u53 value is
+    pair = np.abs(y + S.orc_map(lib, S.COS2, x4, None, np.float64) - 1.0)[exact]
+    out["cos2_pair"] = (float(pair.max()), float(x[exact][pair.argmax()]))
+    x, p = S.pow_cases(n_random // 3)
+    keep = x > 0
+    x, p = x[keep], p[keep]
+    y = S.orc_map(lib, S.POW, x, p, np.float64)
+    errs = []
+    tiny = mp.ldexp(1, -1022)
+    for a, e, b in zip(x.tolist(), p.tolist(), y.tolist()):
+        t = mp.power(mp.mpf(a), mp.mpf(e))
+        errs.append(abs(mp.mpf(b) - t) / max(t, tiny))                      # (relative to the smallest normal once the result is below it)
+    out["pow"] = worst(errs, x)
+    x = S.f32_cases(61 * 4096)
+    x = x[np.isfinite(x)]
+    xe = x[(x >= -87.0) & (x <= 88.0)]
+    y = S.orc_map(lib, S.EXPF, xe, None, np.float32)
+    errs = []
+    for a, b in zip(xe.tolist(), y.tolist()):
+        t = mp.exp(mp.mpf(a))
+        errs.append(abs(mp.mpf(b) - t) / t)
+    out["expf"] = worst(errs, xe)
+    y = S.orc_map(lib, S.TANHF, x, None, np.float32)
+    errs = [abs(mp.mpf(b) - mp.tanh(mp.mpf(a))) for a, b in zip(x.tolist(), y.tolist())]
+    out["tanhf"] = worst(errs, x)
+    return out
+
+
+# name: (worst error measured on the committed lists, bound = 1.5 x that).  Inputs and arithmetic are deterministic: the headroom only
+# absorbs an edit of the lists; a wrong coefficient moves these errors by orders of magnitude.
+DET_MATH_MEASURED = {
+    "log": 3.142, "exp": 2.022, "cos2": 3.226e-16, "pow": 3.141e-14, "expf": 8.71e-8, "tanhf": 1.15e-7,
+}
+
+
+def test_det_math_against_mpmath_on_the_structured_lists():
+    """The oracle's raz-math-v1 against mathematics (mpmath, 200 bits) on the lists the device is compared with the oracle on
+    (tests/spec_cases.py: subnormals, both ends of exp's range, every power of two, the sqrt 2 split, the octants of cos2, pow as
+    the Gamma sampler calls it, a sweep of all float32) - the oracle mirrors the device line for line, so this is what catches a
+    coefficient that is wrong on both sides.  Worst error measured, and where:
+
+        function   worst error                          at
+        log        3.14 ulp                             x = 0x1.9ea93529f947dp-1 (0.8099)
+        exp        2.02 ulp                             x = 0x1.ed8552a93f88dp+4 (30.85)
+        cos2       3.23e-16 absolute                    u = 0x1.df1f17d24a84p-4 (0.1170)
+        pow        3.14e-14 relative                    x = 0x1.2310389d3p-12, y = 1 / 0.03
+        expf       8.71e-8 relative on [-87, 88]        x = -0x1.5bee3ap+6 (-86.98)
+        tanhf      1.15e-7 ABSOLUTE                     x = 0x1.0acp+3 (8.336)
+
+    tanhf is (t - 1) / (t + 1) with t = expf(2|x|): for |x| below about 3e-8 t rounds to 1 and the result is 0, so its RELATIVE error
+    near 0 is unbounded by construction (the value head's output only ever enters sums); the bound is therefore absolute.
+    cos2(u) + cos2(u + 1/4) - 1: measured 0 on the whole list.  Both calls reduce to the same octant argument and differ in the
+    parity of the quadrant alone, so they return s2 and fl(1 - s2) of one s2, whose float sum is within one ulp of 1: bound 2^-52."""
+    got = measure_det_math()
+    for name, (err, arg) in got.items():
+        print(f"{name}: worst error {err:.4g} at {arg!r} ({float(arg).hex()})")
+    for name, measured in DET_MATH_MEASURED.items():
+        assert got[name][0] <= 1.5 * measured, (name, got[name])
+        assert got[name][0] >= measured / 1.5, (name, got[name], "the table in the docstring is out of date")
+    assert got["cos2_pair"][0] <= 2.0 ** -52, got["cos2_pair"]
+    # exact identities
+    lib = O.load_ext()
+    assert lib.orc_det_exp(-746.0) == 0.0 and lib.orc_det_exp(710.0) == float.fromhex("0x1.fffffffffffffp+1023")
+    assert lib.orc_det_exp(0.0) == 1.0 and lib.orc_det_exp(-0.0) == 1.0 and lib.orc_det_log(1.0) == 0.0
+    for bad in (0.0, -0.0, -1.0, float("nan"), float("-inf")):
+        assert lib.orc_det_log(bad) == -1.0e308
+    ulp_half = 2.0 ** -53
+    want = [(1.0, 0.0), (0.5, 2 * ulp_half), (0.0, 2.0 ** -64), (0.5, 2 * ulp_half), (1.0, 0.0), (0.5, 2 * ulp_half), (0.0, 2.0 ** -64), (0.5, 2 * ulp_half)]
+    for j, (v, tol) in enumerate(want):      # the octant logic: 1 and 0 on the axes (exactly 1; sin^2 of the rounded pi/2 is not 0 but ~4e-33), 1/2 to an ulp between
+        c = lib.orc_det_cos2(j / 8.0)
+        assert abs(c - v) <= tol, (j, c)
+        assert (c == 1.0) if v == 1.0 else True
+    assert lib.orc_det_pow(0.0, 3.0) == 0.0 and lib.orc_det_pow(-1.0, 3.0) == 0.0
+
+
+def test_gamma_samplers_at_and_below_one_half_have_the_gamma_distribution():
+    """raz-rng-v1's Gamma(1/2) pair (Box-Muller: E cos^2, E sin^2 of one Philox block - what every shipped config draws its root noise
+    from) and its Gamma(alpha < 1) rejection sampler against scipy's distributions: Kolmogorov-Smirnov over 20 000 samples each, as
+    the alpha > 1 test above.  The two members of a pair must also be independent: their sample correlation stays below 4 / sqrt(n)
+    (four standard deviations of r under independence).  At alpha = 0.03 nearly all the mass lies below 1e-30, where a KS test on x
+    sees one step: it is run on log x against scipy's loggamma."""
+    from scipy import stats
+    lib = O.load_ext()
+    n = 20000
+    g = (ctypes.c_double * 2)()
+    pairs = np.zeros((n, 2))
+    for ev in range(n):
+        lib.orc_dirichlet_gammas(0.5, 2, 11, 5, ev, g)
+        pairs[ev] = g[0], g[1]
+    assert pairs.min() > 0.0
+    for m in (0, 1):
+        assert stats.kstest(pairs[:, m], "gamma", args=(0.5,)).pvalue > 1e-3, m
+    assert stats.kstest(pairs.sum(1), "expon").pvalue > 1e-3                  # g0 + g1 = E ~ Exp(1)
+    r = np.corrcoef(pairs[:, 0], pairs[:, 1])[0, 1]
+    assert abs(r) < 4.0 / np.sqrt(n), r
+    for alpha in (0.03, 0.3, 0.75):
+        xs = np.array([lib.orc_gamma_sample(alpha, 11, 5, ev, ev % 7) for ev in range(n)])
+        assert xs.min() > 0.0
+        if alpha == 0.03:
+            p = stats.kstest(np.log(xs), "loggamma", args=(alpha,)).pvalue
+        else:
+            p = stats.kstest(xs, "gamma", args=(alpha,)).pvalue
+        print(alpha, p)
+        assert p > 1e-3, (alpha, p)
