@@ -392,6 +392,41 @@ int raz_engine_leaf_cache_stats(raz_engine* e, uint64_t* out4, raz_stream_t stre
  *   [13] rounds all slots' solves were listed in, [14] most of one slot (the batch's critical path in rounds of the pool).
  * Synchronises `stream`. */
 int raz_engine_solver_stats(raz_engine* e, uint64_t* out15, raz_stream_t stream);
+/* ---- batched end-game solver: ReversiSolver.solve (lib/alt/reversi_solver_cython.pyx:40-127) for n positions at once ---------------
+ * Independent of any engine (csrc/raz_solver_batch.hip).  Row i is (d_black[i], d_white[i], d_player[i]: 1 black / 2 white to move);
+ * exactly = 0 is the reference's win/loss mode (EVERY node's loop over its moves - ascending, strict improvement - stops at the first
+ * value > 0), exactly != 0 the full scan.  d_status[i]:
+ *   0 solved           d_move[i] 0..63, d_score[i] the disc difference from the side to move's view: the reference's (move, score);
+ *   1 no move          the side to move has no legal move - a root that must pass, a finished game, a full board: the reference's
+ *                      (None, None) (:58-59);
+ *   2 refused          more than 14 empty squares: not searched, never approximated;
+ *   3 not a position   a square of both colours, or a player byte other than 1 / 2 (checked first): not searched;
+ * rows of status 1..3 answer d_move = -1, d_score = -100.  A row's three bytes are a function of (its position, the mode) alone:
+ * the other rows, n, the workspace's size, `tuning` and the stream change no output byte.
+ * d_workspace: 256-byte aligned, at least raz_solve_batch_workspace_bytes(n, e) bytes where e >= the most empty squares of a row
+ * that is searched (14 always suffices; 0 is returned for e > 14 and for n > 2^31: refused).  The size covers the worst case of ONE
+ * row; a larger workspace lets more rows share a pass (the call cuts the batch into chunks that fit).  After the call its first 8
+ * bytes hold the number of node visits (moves played) of the call, as a uint64.
+ * tuning: 0 = the defaults; tests force the partition of the work with
+ *   bits 0-3    leaf size: nodes with more empty squares are split into their children, smaller ones are searched by one lane
+ *               (0 = 8, the largest; 2..8);
+ *   bits 4-7    the most plies the leaf size above is applied for, + 1 (0 = all 6; 1 = none ... 7 = 6 plies).  Below those plies a
+ *               node is split only while it has more than 8 empty squares: that much splitting is not a knob - under every tuning
+ *               one lane searches a subtree of at most 8 empties (at most 109 601 node visits).  "No split" therefore means no
+ *               split of positions of at most 8 empties, and no more than the bound asks for above that;
+ *   bits 8-23   the most rows per chunk (0 = as many as the workspace holds);
+ * any other bit, or a value outside those ranges: RAZ_EINVAL.
+ * RAZ_EINVAL and NO launch: unknown tuning, a NULL or misaligned array, a workspace below raz_solve_batch_workspace_bytes(n, 0).
+ * RAZ_EINVAL with no output byte written: a workspace below raz_solve_batch_workspace_bytes(n, the most empties of a searched row).
+ * The call learns that number from its classification pass, so - unlike the refusals above - this one comes after that pass has been
+ * launched (it writes into the workspace alone) and the stream synchronised.  RAZ_ENOMEM: no host memory for n bytes.
+ * n == 0: RAZ_OK, no launch.  No GPU: RAZ_EDEVICE.
+ * The call SYNCHRONISES `stream` once, after the classification pass (the host sizes the chunks from the rows' empties), and is
+ * therefore not graph-capturable; the search itself is enqueued asynchronously, ordered on `stream`. */
+size_t raz_solve_batch_workspace_bytes(size_t n, int max_empties);
+int raz_solve_batch(const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player, size_t n, int exactly,
+                    int8_t* d_move, int8_t* d_score, uint8_t* d_status, void* d_workspace, size_t workspace_bytes,
+                    uint32_t tuning, raz_stream_t stream);
 /* Diagnostics (no reference counterpart): `bytes` at `offset` of one of the engine's device arrays (raz_engine_device_ptr's numbering:
  * 3 the games' control blocks, 6 the solver blocks, 7 / 8 / 9 the solver pool's lane state / headers / active list) copied to host
  * memory.  RAZ_EINVAL when offset + bytes reaches beyond the array.  Synchronises the device. */

@@ -1,0 +1,93 @@
+"""Drop-in for reversi_zero/lib/reversi_solver.py (compiled form: lib/alt/reversi_solver_cython.pyx:40-127), backed by
+raz_solve_batch (include/raz.h; kernels in csrc/raz_solver_batch.hip): the exact end-game solver for one position - `solve`, the
+reference's signature and answers - or for arrays of positions at once - `solve_batch`.  Device-only, like the batched functions
+of lib/bitboard.py: there is no CPU fallback, and without a GPU the call raises RuntimeError."""
+import numpy as np
+
+from .._native import lib, check, tensor_ptr, current_stream_ptr
+
+MAX_EMPTIES = 14   # the library's declared limit: below turn 46 the reference leans on its 30 s wall-clock time-out
+
+SOLVED, NO_MOVE, TOO_MANY_EMPTIES, NOT_A_POSITION = 0, 1, 2, 3
+
+
+def _player_byte(p):
+    return int(getattr(p, "value", p))   # a Player (env/reversi_env.py) or 1 / 2
+
+
+class ReversiSolver:
+    """calculate which is winner. Not estimation by NN!  (lib/reversi_solver.py:17-21)
+
+    An instance owns ONE workspace and hands it to every call, on whatever stream is current: calls through the same instance
+    must be ordered on one stream (or synchronised by the caller).  Work on several streams at once takes one instance each."""
+
+    def __init__(self, device=None):
+        self._device = device
+        self._ws = None   # the workspace of raz_solve_batch: owned here, grown when a batch needs more, reused otherwise
+
+    def _workspace(self, n, device):
+        import torch
+        least = lib.raz_solve_batch_workspace_bytes(n, MAX_EMPTIES)
+        if least == 0:
+            raise ValueError(f"raz_solve_batch refuses a batch of {n} positions")
+        # above the minimum (one row's worst case) room for whole rows to share a pass: 4 KB a row covers the worst case of 10 empties
+        want = least + min(n * 4096, 1 << 31)
+        if self._ws is None or self._ws.numel() < want or self._ws.device != device:
+            self._ws = torch.empty(want, dtype=torch.uint8, device=device)
+        return self._ws
+
+    def solve_batch(self, black, white, next_player, exactly=False):
+        """Arrays of positions: `black`, `white` int64 / uint64 device tensors (bit i = square i), `next_player` a uint8 device
+        tensor (1 black, 2 white).  Returns device tensors (move int8, score int8, status uint8), one entry per position:
+        status 0 = solved - the reference's (move, score), score from the side to move's view; 1 = the side to move has no legal
+        move (the reference's (None, None)); 2 = refused, more than 14 empty squares; 3 = not a position (a square of both
+        colours, a player byte other than 1 / 2); move = -1 and score = -100 where status != 0.  An answer depends on its
+        position and the mode alone, never on the rest of the batch."""
+        import torch
+        for t in (black, white):
+            if t.dtype not in (torch.int64, torch.uint64):
+                raise TypeError("bitboard tensors must be int64/uint64")
+        if next_player.dtype != torch.uint8:
+            raise TypeError("next_player must be a uint8 tensor")
+        if not (black.is_cuda and white.is_cuda and next_player.is_cuda):
+            raise ValueError("solve_batch is device-only (no CPU fallback)")
+        n = black.numel()
+        if white.numel() != n or next_player.numel() != n:
+            raise ValueError("black, white and next_player must have the same number of elements")
+        move = torch.empty(n, dtype=torch.int8, device=black.device)
+        score = torch.empty(n, dtype=torch.int8, device=black.device)
+        status = torch.empty(n, dtype=torch.uint8, device=black.device)
+        if n:
+            ws = self._workspace(n, black.device)
+            check(lib.raz_solve_batch(tensor_ptr(black), tensor_ptr(white), tensor_ptr(next_player), n, int(bool(exactly)),
+                                      tensor_ptr(move), tensor_ptr(score), tensor_ptr(status), tensor_ptr(ws), ws.numel(), 0,
+                                      current_stream_ptr()), "raz_solve_batch")
+        return move, score, status
+
+    def solve(self, black, white, next_player, timeout=30, exactly=False):
+        """ReversiSolver.solve (lib/alt/reversi_solver_cython.pyx:40-61): (move, score) with score the disc difference from the
+        side to move's view, or (None, None) when the side to move has no legal move.  exactly=False is the win/loss mode (every
+        node's scan stops at its first winning move), True the full scan.
+
+        `timeout` is accepted and ignored: the reference gives up - (None, None) - when its wall clock runs out, so its answer
+        depends on the host's speed; here the answer is a function of the position and the mode alone.  What the reference could
+        only try under its time-out is refused instead: more than 14 empty squares raises ValueError, and so does a position
+        with a square of both colours."""
+        import torch
+        device = torch.device(self._device or "cuda")
+        player = _player_byte(next_player)
+        if player not in (1, 2):
+            raise ValueError(f"next_player must be Player.black / Player.white or 1 / 2, not {next_player!r}")
+        m64 = (1 << 64) - 1
+        b = torch.from_numpy(np.array([int(black) & m64], dtype=np.uint64).view(np.int64)).to(device)
+        w = torch.from_numpy(np.array([int(white) & m64], dtype=np.uint64).view(np.int64)).to(device)
+        p = torch.tensor([player], dtype=torch.uint8, device=device)
+        move, score, status = (int(t.cpu()[0]) for t in self.solve_batch(b, w, p, exactly=exactly))
+        if status == TOO_MANY_EMPTIES:
+            raise ValueError(f"the solver takes positions of at most {MAX_EMPTIES} empty squares "
+                             f"(this one has {64 - bin((int(black) | int(white)) & m64).count('1')})")
+        if status == NOT_A_POSITION:
+            raise ValueError("not a position: a square holds a disc of both colours")
+        if status == NO_MOVE:
+            return None, None
+        return move, score
