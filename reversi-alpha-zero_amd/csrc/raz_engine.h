@@ -78,8 +78,7 @@ struct raz_solve_hdr {           // 64 bytes at the start of a game's solver blo
     uint32_t k_n2, tasks, total; // root moves | level-2 nodes << 8; level-3 nodes; subtrees the workers search (the tasks)
     uint32_t next;               // next task to hand out (workers: atomicAdd)
     int32_t ans_move;            // (a copy of what the state word carries: diagnostics)
-    uint32_t limit;              // tasks [0, limit) may be handed out in this round (k_solve_scan: every task of an exact solve; of a win/loss
-                                 // solve the tasks below the first RAZ_SOLVER_NE_WINDOW root moves that are still open)
+    uint32_t limit;              // reserved: nothing writes or reads it (it was the task window of a win/loss solve; the layout stays)
     uint32_t posted;             // requests this game slot has posted since raz_engine_start (the tree kernels' word; statistics)
     uint32_t rounds;             // rounds of the pool the solve has been listed in (statistics)
     uint32_t rounds_total;       // ... and all solves of this game slot since raz_engine_start
@@ -91,7 +90,7 @@ static_assert(__builtin_offsetof(raz_solve_hdr, state) == 0 && __builtin_offseto
 #define RAZ_SOLVER_TREE_BYTES 12288   // >= sizeof(SolverTree) (raz_solver_pool.h, checked there): the top three plies, folded in LDS
 #define RAZ_SOLVER_DEEP_BYTES 135168  // >= sizeof(SolverDeep): the positions three plies down and, below the larger ones, a fourth ply of tasks
 #define RAZ_SOLVER_WS_BYTES (64 + RAZ_SOLVER_TREE_BYTES + RAZ_SOLVER_DEEP_BYTES)
-// a worker wave of the pool: 16 words of lane state (the search in hand and the task drawn ahead) and 14 frames of 32 B per lane
+// a worker wave of the pool: 16 words of lane state (words 0-5 hold the search in hand, the rest are spare) and 14 frames of 32 B per lane
 #define RAZ_SOLVER_WORKER_STATE_BYTES (16 * 64 * 8)
 #define RAZ_SOLVER_WORKER_FRAME_BYTES (14 * 64 * 32)
 struct raz_solver_pool_hdr {     // one per slice of the batch (64 bytes)

@@ -584,7 +584,8 @@ __device__ __forceinline__ float masked_normalised_prior(float pol, raz_bb legal
 //   * positions with <= RAZ_SOLVER_SCALAR_EMPTIES empties: right here, one wave-uniform DFS on the scalar unit, frames in LDS;
 //   * larger ones (<= RAZ_SOLVER_MAX_DEPTH empties): the tree kernel only POSTS the position in its game's request block and
 //     suspends (RAZ_SOLVE_PENDING); the solver pool (raz_solver_pool.h: k_solve_scan / k_solve_run, launched between tree
-//     launches) answers it, and the next call for the same position returns the answer;
+//     launches; its lanes run the per-lane statement of raz_solver_search.h, which raz_solve_batch shares) answers it, and the
+//     next call for the same position returns the answer;
 //   * a per-game memo in HBM (positions with >= 4 empties; it only saves time, exactly as the reference's dict does) is shared by
 //     all of them.
 // f is a function of the position, so WHEN an answer arrives changes nothing but a game's wall time.

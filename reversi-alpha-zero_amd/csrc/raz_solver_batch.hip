@@ -25,11 +25,12 @@
 // the leaf size, the number of plies split or the order in which the atomics hand out records: a record's children are found
 // through the parent (first child, count), never through their own numbers' order across parents.  In win/loss mode subtrees the
 // sequential scan would have skipped are searched too; their values are never read (the fold's scan stops where the reference's
-// stops).  No memo.  Measurements: DESIGN.md 4.7.
+// stops).  No memo.  The search itself (the move function, the scan, a lane's node and its frame word) is raz_solver_search.h's,
+// the same statement the pool's lanes run: one statement, two drivers.  Measurements: DESIGN.md 4.7.
 #include <exception>
 #include <vector>
-#include "raz_bitboard_valu.h"
 #include "raz_internal.h"
+#include "raz_solver_search.h"   // the per-lane search itself: solver_play, solver_scan, SolverNode (shared with raz_solver_pool.h)
 
 namespace {
 
@@ -37,7 +38,7 @@ namespace {
 #define SB_MAX_LEAF 8        // a lane's subtree: <= 8 empties
 #define SB_MIN_LEAF 2
 #define SB_MAX_PLIES 6       // 14 - 8: plies the split may go down
-#define SB_UNKNOWN (-128)
+#define SB_UNKNOWN RAZ_SOLVER_UNKNOWN
 #define SB_HDR_BYTES 256
 #define SB_REC_BYTES 24
 #define SB_TUNING_MASK 0x00ffffffu
@@ -70,38 +71,6 @@ __device__ __forceinline__ uint32_t sb_meta(int value, int move, int kind, int e
 }
 __device__ __forceinline__ int sb_value(uint32_t m) { return (int)(m & 0xffu) - 128; }
 __device__ __forceinline__ int sb_kind(uint32_t m) { return (int)((m >> 16) & 3u); }
-
-// one empty square e, `own` to move: the final disc difference for `own` (env/reversi_env.py:68-85)
-__device__ __forceinline__ int sb_last_one(int e, raz_bb own, raz_bb enemy) {
-    const int f = bb_popcount(bbv_calc_flip(e, own, enemy));
-    const int po = bb_popcount(own), pe = bb_popcount(enemy);
-    if (f) return (po + f + 1) - (pe - f);
-    const int g = bb_popcount(bbv_calc_flip(e, enemy, own));
-    return g ? (po - g) - (pe + g + 1) : po - pe;
-}
-// `mover` (own, enemy) plays square a.  0: the game ends there, or one square is left and is finished here (v = the final disc
-// difference for `mover`); 1: the opponent moves; 2: the opponent passes; (no, ne, nm) = the next position from ITS mover's view
-__device__ __forceinline__ int sb_play(int a, raz_bb own, raz_bb enemy, raz_bb& no, raz_bb& ne, raz_bb& nm, int& v) {
-    const raz_bb flipped = bbv_calc_flip(a, own, enemy);
-    const raz_bb nown = (own ^ flipped) | (1ULL << a), nenemy = enemy ^ flipped;
-    const raz_bb l1 = bbv_legal_moves(nenemy, nown);
-    const raz_bb l2 = l1 ? 0ULL : bbv_legal_moves(nown, nenemy);
-    no = ne = nm = 0ULL;
-    if (!(l1 | l2)) {
-        v = bb_popcount(nown) - bb_popcount(nenemy);
-        return 0;
-    }
-    if (bb_popcount(~(nown | nenemy)) == 1) {   // a node with one move has nothing to choose and nothing to cut off
-        const int e = __ffsll((long long)(l1 | l2)) - 1;
-        v = l1 ? -sb_last_one(e, nenemy, nown) : sb_last_one(e, nown, nenemy);
-        return 0;
-    }
-    no = l1 ? nenemy : nown;
-    ne = l1 ? nown : nenemy;
-    nm = l1 ? l1 : l2;
-    v = 0;
-    return l1 ? 1 : 2;
-}
 
 constexpr int kBlock = 256;
 
@@ -146,7 +115,7 @@ __global__ __launch_bounds__(64) void k_sb_mark(SbWs W, int p) {
 
 // a record of level p is expanded when it has more than SB_MAX_LEAF empties (the bound on a lane's work: whatever the tuning), or
 // more than `leaf` and p < plies (a finer split: the default leaf is SB_MAX_LEAF, where both say the same)
-__global__ __launch_bounds__(kBlock) void k_sb_expand(SbWs W, int p, int leaf, int plies) {
+__global__ __launch_bounds__(kBlock) void k_sb_expand(SbWs W, int p, int leaf, int plies, uint32_t exact) {
     const uint32_t lo = W.hdr->level[p], hi = W.hdr->level[p + 1], stride = gridDim.x * kBlock;
     uint32_t visits = 0u;
     for (uint32_t i = lo + blockIdx.x * kBlock + threadIdx.x; i < hi; i += stride) {
@@ -165,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void k_sb_expand(SbWs W, int p, int leaf, i
         for (raz_bb l = moves; l; l &= l - 1, ++c) {
             raz_bb no, ne, nm;
             int v;
-            const int kind = sb_play(__ffsll((long long)l) - 1, own, enemy, no, ne, nm, v);
+            const int kind = solver_play(__ffsll((long long)l) - 1, own, enemy, no, ne, nm, v, exact != 0u);
             W.own[c] = no;
             W.enemy[c] = ne;
             W.first[c] = 0u;
@@ -178,19 +147,36 @@ __global__ __launch_bounds__(kBlock) void k_sb_expand(SbWs W, int p, int leaf, i
     if (visits) atomicAdd(&W.hdr->visits, (unsigned long long)visits);
 }
 
-// FRAMES: the deepest stack a task needs - a node has at least two empty squares (the last one is finished by sb_play), so a task
-// of e <= SB_MAX_LEAF empties pushes at most e - 2 frames
+// FRAMES: the deepest stack a task needs - a node has at least two empty squares (the last one is finished by solver_play), so a
+// task of e <= SB_MAX_LEAF empties pushes at most e - 2 frames
 constexpr int FRAMES = SB_MAX_LEAF - 2;
+static_assert(RAZ_SOLVER_INLINE_LAST >= 1, "FRAMES rests on solver_play finishing the last empty square itself");
+struct SbFrames {   // a lane's column of the wave's frames: level d = three 8-byte words (own, enemy, moves left) and SolverNode's frame word
+    unsigned long long* f64;   // word j of level d: f64[(d * 3 + j) * 64]
+    uint32_t* f32;             // f32[d * 64]
+    __device__ __forceinline__ void put(int d, raz_bb own, raz_bb enemy, raz_bb left, uint32_t word) const {
+        f64[(d * 3 + 0) * 64] = own;
+        f64[(d * 3 + 1) * 64] = enemy;
+        f64[(d * 3 + 2) * 64] = left;
+        f32[d * 64] = word;
+    }
+    __device__ __forceinline__ void get(int d, raz_bb& own, raz_bb& enemy, raz_bb& left, uint32_t& word) const {
+        own = f64[(d * 3 + 0) * 64];
+        enemy = f64[(d * 3 + 1) * 64];
+        left = f64[(d * 3 + 2) * 64];
+        word = f32[d * 64];
+    }
+};
 __global__ __launch_bounds__(64) void k_sb_leaves(SbWs W, uint32_t exact) {
-    __shared__ unsigned long long fr64[FRAMES * 3 * 64];   // word j of level d of lane l: fr64[(d * 3 + j) * 64 + l] (own, enemy, moves left)
-    __shared__ uint32_t fr32[FRAMES * 64];                 // best move + 1 | best score + 128 << 8 | the move that led here + 1 << 16 | sign flips << 24
+    __shared__ unsigned long long fr64[FRAMES * 3 * 64];
+    __shared__ uint32_t fr32[FRAMES * 64];
     const int lane = threadIdx.x;
-    unsigned long long* f64 = fr64 + lane;
-    uint32_t* f32 = fr32 + lane;
+    const SbFrames frames{fr64 + lane, fr32 + lane};
     const uint32_t total = W.hdr->count < W.cap ? W.hdr->count : W.cap;
     bool have = false, dry = false;
-    raz_bb own = 0, enemy = 0, left = 0;
-    int d = 0, bmv = -1, bsc = -100, pact = -1, flip = 0;
+    SolverNode nd;   // the node the lane's search stands on
+    nd.begin(0ULL, 0ULL, 0ULL);
+    int d = 0;
     uint32_t task = 0u, task_meta = 0u;
     unsigned long long visits = 0ULL;
     for (uint32_t it = 0u;; ++it) {
@@ -209,14 +195,9 @@ __global__ __launch_bounds__(64) void k_sb_leaves(SbWs W, uint32_t exact) {
                 if (sb_kind(m) != 0 && !((m >> 18) & 1u)) {
                     task = t;
                     task_meta = m;
-                    own = W.own[t];
-                    enemy = W.enemy[t];
-                    left = bbv_legal_moves(own, enemy);
+                    const raz_bb own = W.own[t], enemy = W.enemy[t];
+                    nd.begin(own, enemy, bbv_legal_moves(own, enemy));
                     d = 0;
-                    bmv = -1;
-                    bsc = -100;
-                    pact = -1;
-                    flip = 0;
                     have = true;
                 }
             }
@@ -226,55 +207,22 @@ __global__ __launch_bounds__(64) void k_sb_leaves(SbWs W, uint32_t exact) {
             // loop as its deepest unwinding lane needs), then the node the search stands on plays its next move
             bool may_move = false;
             for (int returns = 0; returns <= 2; ++returns) {
-                if (!(left == 0ULL || (!exact && bsc > 0))) {
+                if (!nd.finished(exact != 0u)) {
                     may_move = true;
                     break;
                 }
                 if (returns == 2) break;
                 if (d == 0) {
-                    W.meta[task] = sb_meta(sb_kind(task_meta) == 1 ? -bsc : bsc, bmv, sb_kind(task_meta), 0, 0);
+                    W.meta[task] = sb_meta(sb_kind(task_meta) == 1 ? -nd.bsc : nd.bsc, nd.bmv, sb_kind(task_meta), 0, 0);
                     have = false;
                     break;
                 }
-                const int v = flip ? -bsc : bsc, a = pact;
-                --d;
-                own = f64[(d * 3 + 0) * 64];
-                enemy = f64[(d * 3 + 1) * 64];
-                left = f64[(d * 3 + 2) * 64];
-                const uint32_t fm = f32[d * 64];
-                bmv = (int)(fm & 0xffu) - 1;
-                bsc = (int)((fm >> 8) & 0xffu) - 128;
-                pact = (int)((fm >> 16) & 0xffu) - 1;
-                flip = (int)((fm >> 24) & 1u);
-                if (bsc < v) {
-                    bmv = a;
-                    bsc = v;
-                }
+                nd.give_to_parent(frames, d, nd.bsc);
             }
             if (have && may_move) {
-                const int a = __ffsll((long long)left) - 1;
-                left &= left - 1;
-                raz_bb no, ne, nm;
-                int score;
-                const int kind = sb_play(a, own, enemy, no, ne, nm, score);
+                // (d < FRAMES always holds: see above; the test keeps the stores inside the arrays)
+                nd.play_next(frames, d, exact != 0u, d < FRAMES);
                 ++visits;
-                if (kind && d < FRAMES) {   // down a ply (d < FRAMES always holds: see above; the test keeps the stores inside the arrays)
-                    f64[(d * 3 + 0) * 64] = own;
-                    f64[(d * 3 + 1) * 64] = enemy;
-                    f64[(d * 3 + 2) * 64] = left;
-                    f32[d * 64] = (uint32_t)(bmv + 1) | ((uint32_t)(bsc + 128) << 8) | ((uint32_t)(pact + 1) << 16) | ((uint32_t)flip << 24);
-                    ++d;
-                    own = no;
-                    enemy = ne;
-                    left = nm;
-                    bmv = -1;
-                    bsc = -100;
-                    pact = a;
-                    flip = kind == 1 ? 1 : 0;
-                } else if (bsc < score) {
-                    bmv = a;
-                    bsc = score;
-                }
             }
         }
     }
@@ -282,8 +230,8 @@ __global__ __launch_bounds__(64) void k_sb_leaves(SbWs W, uint32_t exact) {
     if (lane == 0 && visits) atomicAdd(&W.hdr->visits, visits);
 }
 
-// level p: the reference's loop over a node's moves - ascending, strict improvement, win/loss mode done at the first value > 0 -
-// on the children's values (all of them are there; the ones behind a decided scan are not read)
+// level p: the reference's loop over a node's moves (solver_scan) on the children's values (all of them are there; the ones
+// behind a decided scan are not read)
 __global__ __launch_bounds__(kBlock) void k_sb_fold(SbWs W, int p, uint32_t exact) {
     const uint32_t lo = W.hdr->level[p], hi = W.hdr->level[p + 1], stride = gridDim.x * kBlock;
     for (uint32_t i = lo + blockIdx.x * kBlock + threadIdx.x; i < hi; i += stride) {
@@ -291,16 +239,8 @@ __global__ __launch_bounds__(kBlock) void k_sb_fold(SbWs W, int p, uint32_t exac
         if (!((m >> 18) & 1u)) continue;
         const int nch = (int)((m >> 19) & 31u);
         const uint32_t first = W.first[i];
-        raz_bb l = bbv_legal_moves(W.own[i], W.enemy[i]);
-        int bm = -1, bs = -100;
-        for (int j = 0; j < nch; ++j, l &= l - 1) {
-            const int v = sb_value(W.meta[first + j]);
-            if (bs < v) {
-                bm = __ffsll((long long)l) - 1;
-                bs = v;
-            }
-            if (!exact && bs > 0) break;
-        }
+        int bm, bs;
+        solver_scan([&](int j) { return sb_value(W.meta[first + j]); }, nch, bbv_legal_moves(W.own[i], W.enemy[i]), exact != 0u, bm, bs);
         W.meta[i] = sb_meta(sb_kind(m) == 1 ? -bs : bs, bm, sb_kind(m), 1, nch);
     }
 }
@@ -418,7 +358,7 @@ extern "C" int raz_solve_batch(const uint64_t* d_black, const uint64_t* d_white,
         const uint32_t rows = (uint32_t)(r1 - r0);
         hipLaunchKernelGGL(k_sb_roots, dim3(sb_grid(rows, kBlock, 2048)), dim3(kBlock), 0, s, W, bl, wh, d_player, r0, rows);
         for (int p = 0; p < chunk_plies; ++p) {
-            hipLaunchKernelGGL(k_sb_expand, dim3(sb_grid(used, kBlock, 2048)), dim3(kBlock), 0, s, W, p, leaf, plies);
+            hipLaunchKernelGGL(k_sb_expand, dim3(sb_grid(used, kBlock, 2048)), dim3(kBlock), 0, s, W, p, leaf, plies, (uint32_t)(exactly != 0));
             hipLaunchKernelGGL(k_sb_mark, dim3(1), dim3(64), 0, s, W, p);
         }
         hipLaunchKernelGGL(k_sb_leaves, dim3(sb_grid(used, 64, 3072)), dim3(64), 0, s, W, (uint32_t)(exactly != 0));

@@ -26,15 +26,16 @@
 // f is a function of (position, mode): which lane searches a subtree, in which launch, or whether a subtree the sequential scan
 // would have skipped is searched as well changes no answer.  Workers never talk to each other inside a launch (only the solves' task
 // counters and the claim of a memo slot are atomic); everything else crosses kernel boundaries.  Measurements: DESIGN.md 4.7.
+// The search a lane runs - what a move leads to, a node's scan over its children's values, the node and its frame word - is stated in
+// raz_solver_search.h, once for this pool and for raz_solve_batch (raz_solver_batch.hip); here are the task tree, the memo, the draws.
 #pragma once
 #include "raz_engine_core.h"
-#include "raz_bitboard_valu.h"   // the per-LANE forms of the bitboard primitives (same results for every input)
+#include "raz_solver_search.h"   // the per-lane search itself: solver_play, solver_scan, SolverNode (shared with raz_solver_batch.hip)
 
 namespace {
 
 #define RAZ_SOLVER_MAX_L2 (RAZ_SOLVER_MAX_DEPTH * (RAZ_SOLVER_MAX_DEPTH - 1))        // 182 positions two plies below the root
 #define RAZ_SOLVER_MAX_TASKS (RAZ_SOLVER_MAX_L2 * (RAZ_SOLVER_MAX_DEPTH - 2))        // 2184 subtrees three plies below it
-#define RAZ_SOLVER_UNKNOWN (-128)
 struct SolverTree {   // in the game's block of E.solver_ws behind the header; k_solve_scan works on a copy in LDS
     unsigned long long c_own[RAZ_SOLVER_MAX_DEPTH], c_enemy[RAZ_SOLVER_MAX_DEPTH], c_moves[RAZ_SOLVER_MAX_DEPTH];   // child i: position (its mover's view), its moves
     unsigned long long g_own[RAZ_SOLVER_MAX_L2], g_enemy[RAZ_SOLVER_MAX_L2], g_moves[RAZ_SOLVER_MAX_L2];           // level-2 node n, likewise
@@ -74,104 +75,6 @@ __device__ __forceinline__ SolverTree* solve_tree(const raz_engine_dev& E, uint3
 __device__ __forceinline__ SolverDeep* solve_deep(const raz_engine_dev& E, uint32_t g) {
     return (SolverDeep*)(E.solver_ws + (size_t)g * RAZ_SOLVER_WS_BYTES + sizeof(raz_solve_hdr) + RAZ_SOLVER_TREE_BYTES);
 }
-
-// the reference's loop over a node's moves, on values that are already there: `vals` in ascending move order, RAZ_SOLVER_UNKNOWN =
-// not there yet.  Returns false while the scan is not decided.  Non-exact: it ends at the first value > 0
-__device__ __forceinline__ bool solver_scan(const signed char* vals, int n, raz_bb moves, bool exact, int& bm, int& bs) {
-    bm = -1;
-    bs = -100;
-    raz_bb m = moves;
-    for (int j = 0; j < n; ++j, m &= m - 1) {
-        const int v = vals[j];
-        if (v == RAZ_SOLVER_UNKNOWN) return false;
-        if (bs < v) {
-            bm = __ffsll((long long)m) - 1;
-            bs = v;
-        }
-        if (!exact && bs > 0) break;
-    }
-    return true;
-}
-
-// a position after `mover` (own, enemy) played square a: who moves next.  kind 0: the game ends (v = disc difference for `mover`);
-// 1: the opponent moves; 2: the opponent passes (the mover again); (no, ne, nm) = the next position from ITS mover's view and its moves
-// RAZ_SOLVER_INLINE_LAST: a position with ONE empty square left is not handed back as a node - it would cost the worker wave a whole
-// iteration to play its only move - but finished here: whoever can play the square plays it (one more calc_flip), the discs are counted,
-// and the move reports "the game ends there" with that count.  The same value the two steps give (a node with one move has nothing to
-// choose and nothing to cut off); in a full-width search every second node is such a node.
-#ifndef RAZ_SOLVER_INLINE_LAST
-#define RAZ_SOLVER_INLINE_LAST 1   // 2: positions with TWO empty squares are finished in the move function too (solver_last_two)
-// Measured on mini.yml as shipped (M sims/s: two-kernel lock-step / continuous batching / fused lock-step; tools/sessions/r6_s22-24.sh,
-// profiles/r6/solver_last_squares_finished_in_the_move_function_ab.json), level x iterations per round:
-//   0 x 128: 31.2 / 31.4 / 25.4 (4.61 rounds per answer)     1 x 128: 33.7 / 32.6 / 29.5 (3.28)     1 x 96: 34.2 / 33.7 / 27.5     1 x 64: 33.6 / 32.9 / 23.7
-//   2 x 128: 32.0 / 30.6 / 32.1 (2.15: fewer, longer iterations - a round of 128 takes too long)     2 x 96: 33.2 / 31.6 / 30.4     2 x 80: 33.8 / 32.5 / 29.5     2 x 64: 33.8 / 33.3 / 27.7
-// Level 1 at 96 iterations per round is the default (the worker runs the two-kernel pipeline with continuous batching when the solver is on).
-#endif
-// one empty square e, `own` to move: the final disc difference for `own` (env/reversi_env.py:68-85: the mover plays it if that flips
-// something, else the opponent does, else the game is over as it stands)
-__device__ __forceinline__ int solver_last_one(int e, raz_bb own, raz_bb enemy) {
-    const int f = bb_popcount(bbv_calc_flip(e, own, enemy));
-    const int po = bb_popcount(own), pe = bb_popcount(enemy);
-    if (f) return (po + f + 1) - (pe - f);
-    const int g = bb_popcount(bbv_calc_flip(e, enemy, own));
-    return g ? (po - g) - (pe + g + 1) : po - pe;
-}
-// two empty squares, `own` to move with the legal moves `moves` (not empty): the reference's loop over them (ascending, strict
-// improvement, non-exact: done at the first value > 0) with each reply finished by solver_last_one
-__device__ __forceinline__ int solver_last_two(raz_bb moves, raz_bb own, raz_bb enemy, bool exact) {
-    const raz_bb empties = ~(own | enemy);
-    int bs = -100;
-    for (raz_bb m = moves; m; m &= m - 1) {
-        const int s = __ffsll((long long)m) - 1;
-        const raz_bb fl = bbv_calc_flip(s, own, enemy);
-        const raz_bb o2 = (own ^ fl) | (1ULL << s), e2 = enemy ^ fl;
-        const int val = -solver_last_one(__ffsll((long long)(empties & ~(1ULL << s))) - 1, e2, o2);
-        if (bs < val) bs = val;
-        if (!exact && bs > 0) break;
-    }
-    return bs;
-}
-__device__ __forceinline__ int solver_play(int a, raz_bb own, raz_bb enemy, raz_bb& no, raz_bb& ne, raz_bb& nm, int& v, bool exact) {
-    const raz_bb flipped = bbv_calc_flip(a, own, enemy);
-    const raz_bb nown = (own ^ flipped) | (1ULL << a), nenemy = enemy ^ flipped;
-    const raz_bb l1 = bbv_legal_moves(nenemy, nown);
-    const raz_bb l2 = l1 ? 0ULL : bbv_legal_moves(nown, nenemy);
-    if (!(l1 | l2)) {
-        v = bb_popcount(nown) - bb_popcount(nenemy);
-        no = ne = nm = 0ULL;
-        return 0;
-    }
-    if (RAZ_SOLVER_INLINE_LAST >= 2 && bb_popcount(~(nown | nenemy)) == 2) {
-        // two squares left: the node's mover is the opponent if it can move (l1), else the mover of this move again (l2)
-        const bool opp = l1 != 0ULL;
-        const int nv = solver_last_two(l1 | l2, opp ? nenemy : nown, opp ? nown : nenemy, exact);
-        v = opp ? -nv : nv;
-        no = ne = nm = 0ULL;
-        return 0;
-    }
-    if (RAZ_SOLVER_INLINE_LAST && bb_popcount(~(nown | nenemy)) == 1) {
-        // the last square: the opponent's if it can play it (l1), else the mover's again (l2)
-        const bool opp = l1 != 0ULL;
-        const raz_bb last_own = opp ? nenemy : nown, last_enemy = opp ? nown : nenemy;
-        const int f = bb_popcount(bbv_calc_flip(__ffsll((long long)(l1 | l2)) - 1, last_own, last_enemy));
-        const int last = bb_popcount(last_own) + f + 1, other = bb_popcount(last_enemy) - f;
-        v = opp ? other - last : last - other;   // (for the mover of THIS move)
-        no = ne = nm = 0ULL;
-        return 0;
-    }
-    no = l1 ? nenemy : nown;
-    ne = l1 ? nown : nenemy;
-    nm = l1 ? l1 : l2;
-    v = 0;
-    return l1 ? 1 : 2;
-}
-
-#ifndef RAZ_SOLVER_DRAW_GATE
-#define RAZ_SOLVER_DRAW_GATE 1   // idle lanes draw tasks in proportion to the tasks left (k_solve_run, "idle lanes draw tasks"); 0: every idle lane at every slow phase
-#endif
-#ifndef RAZ_SOLVER_NE_WINDOW
-#define RAZ_SOLVER_NE_WINDOW 0   // open root moves of a win/loss solve whose tasks are handed out; 0: all of them at once (the default: see k_solve_scan)
-#endif
 
 // ------------------------------------------------------------------ k_solve_scan
 // collect = 1 (before k_solve_run): new requests get their task tree, every solve with tasks left is listed as active.
@@ -357,7 +260,7 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
                 bs = D->sub_result[s0];
                 ok = bs != RAZ_SOLVER_UNKNOWN;
             } else
-                ok = solver_scan(D->sub_result + s0, s1 - s0, D->h_moves[t], exact != 0, bm, bs);
+                ok = solver_scan([&](int j) { return (int)D->sub_result[s0 + j]; }, s1 - s0, D->h_moves[t], exact != 0, bm, bs);
             if (ok) {
                 if (!(kind & 8)) {
                     const raz_bb ho = D->h_own[t], he = D->h_enemy[t];
@@ -377,7 +280,7 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
         if (P->g_v[n] == RAZ_SOLVER_UNKNOWN && (gk & 3) && !(gk & 4)) {
             const int t0 = P->g_first[n];
             int bm, bs;
-            if (solver_scan(P->result + t0, (int)P->g_first[n + 1] - t0, P->g_moves[n], exact != 0, bm, bs)) {
+            if (solver_scan([&](int j) { return (int)P->result[t0 + j]; }, (int)P->g_first[n + 1] - t0, P->g_moves[n], exact != 0, bm, bs)) {
                 const raz_bb go = P->g_own[n], ge = P->g_enemy[n];
                 if (bb_popcount(~(go | ge)) >= 4) memo_put_lane(E, g, go, ge, exact, bm, bs);
                 P->g_v[n] = (signed char)((gk & 1) ? -bs : bs);
@@ -391,7 +294,7 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
         if (P->c_v[lane] == RAZ_SOLVER_UNKNOWN && (ck & 3) && !(ck & 4)) {
             const int n0 = P->c_first[lane];
             int bm, bs;
-            if (solver_scan(P->g_v + n0, (int)P->c_first[lane + 1] - n0, P->c_moves[lane], exact != 0, bm, bs)) {
+            if (solver_scan([&](int j) { return (int)P->g_v[n0 + j]; }, (int)P->c_first[lane + 1] - n0, P->c_moves[lane], exact != 0, bm, bs)) {
                 const raz_bb co = P->c_own[lane], ce = P->c_enemy[lane];
                 if (bb_popcount(~(co | ce)) >= 4) memo_put_lane(E, g, co, ce, exact, bm, bs);
                 P->c_v[lane] = (signed char)((ck & 1) ? -bs : bs);
@@ -400,20 +303,9 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
     }
     wave_sync_lanes();
     // ---- the root (every lane runs the same scan over LDS: the outcome is wave-uniform)
-    int bm = -1, bs = -100;
-    bool decided = true;
-    for (int i = 0; i < k; ++i) {
-        const int v = P->c_v[i];
-        if (v == RAZ_SOLVER_UNKNOWN) {
-            decided = false;
-            break;
-        }
-        if (bs < v) {
-            bm = P->c_a[i];
-            bs = v;
-        }
-        if (!exact && bs > 0) break;
-    }
+    // (c_a[i], the square of its i-th move, is the i-th bit of its legal moves)
+    int bm, bs;
+    bool decided = solver_scan([&](int i) { return (int)P->c_v[i]; }, k, bb_legal_moves(own0, enemy0), exact != 0, bm, bs);
     decided = uni((uint32_t)decided) != 0u;
     if (decided) {
         bm = uni(bm);
@@ -451,25 +343,6 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
         const bool dead = P->result[t] != RAZ_SOLVER_UNKNOWN || (!exact && (P->g_v[te & 0xff] != RAZ_SOLVER_UNKNOWN || P->c_v[te >> 8] != RAZ_SOLVER_UNKNOWN));
         if (dead) D->h_dead[t] = 1;
     }
-    // A win/loss solve (the reference's `not exactly`: a node's loop ends at the first move with a value > 0) needs the root's moves
-    // one after the other: the subtrees below the third open move matter only if the first two both fail, and the pool spends 21 500
-    // lane-iterations per solve where the reference's own search visits ~1 250 nodes.  RAZ_SOLVER_NE_WINDOW = n releases only the tasks
-    // below the first n open root moves and moves the window on as scans decide them.  MEASURED, round 6 (mini.yml as shipped, one box,
-    // profiles/r6/solver_win_loss_task_window_ab.jsonl): 0 / 1 / 2 / 3 open moves = 21.8 / 13.2 / 17.3 / 19.4 M sims/s lock-step, 27.5 /
-    // 18.1 / 21.9 / 24.3 M with continuous batching - the busy lane-iterations fall by 6 % only (the discarded work sits below the
-    // replies, not below the root's later moves) while every solve needs more rounds.  Kept as a compile-time knob, off.
-    // (the limit is a LEVEL-3 NODE number, read off the tree in LDS: tasks of the nodes [0, limit) are released)
-    uint32_t limit = (uint32_t)total;
-    if (!exact && RAZ_SOLVER_NE_WINDOW > 0) {
-        int open = 0, last = k - 1;
-        for (int i = 0; i < k; ++i)
-            if (P->c_v[i] == RAZ_SOLVER_UNKNOWN && ++open == RAZ_SOLVER_NE_WINDOW) {
-                last = i;
-                break;
-            }
-        limit = (uint32_t)uni((uint32_t)P->g_first[P->c_first[last + 1]]);
-    }
-    if (lane == 0) h->limit = limit;
     if (collect) {
         const uint32_t next = st == RAZ_SOLVE_REQUESTED ? 0u : uni(h->next);
         if (next < (uint32_t)subs && lane == 0) E.pool_active[g0 + atomicAdd(&ph->n_active, 1u)] = g;
@@ -494,9 +367,6 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
 #ifndef RAZ_SOLVER_MAX_RETURNS
 #define RAZ_SOLVER_MAX_RETURNS 2
 #endif
-#ifndef RAZ_SOLVER_PROBE_AT_DRAW
-#define RAZ_SOLVER_PROBE_AT_DRAW 0
-#endif
 #ifndef RAZ_SOLVER_SLOW_EVERY
 #define RAZ_SOLVER_SLOW_EVERY 16   // (a power of two; 4 / 8 / 16: 22.6 / 23.3 / 23.1 M at memo 6, 24.8 M at 16 with memo 7)
 #endif
@@ -506,6 +376,21 @@ __global__ __launch_bounds__(64) void k_solve_scan(raz_engine_dev E, uint32_t g0
 #ifndef RAZ_SOLVER_POOL_BUDGET
 #define RAZ_SOLVER_POOL_BUDGET 96   // (128 until the move function finished the last square itself: see RAZ_SOLVER_INLINE_LAST)
 #endif
+struct PoolFrames {   // a lane's column of the worker wave's frames: level d = four 8-byte words (own, enemy, moves left, SolverNode's frame word)
+    unsigned long long* fr;
+    __device__ __forceinline__ void put(int d, raz_bb own, raz_bb enemy, raz_bb left, uint32_t word) const {
+        fr[(d * 4 + 0) * 64] = own;
+        fr[(d * 4 + 1) * 64] = enemy;
+        fr[(d * 4 + 2) * 64] = left;
+        fr[(d * 4 + 3) * 64] = (unsigned long long)word;
+    }
+    __device__ __forceinline__ void get(int d, raz_bb& own, raz_bb& enemy, raz_bb& left, uint32_t& word) const {
+        own = fr[(d * 4 + 0) * 64];
+        enemy = fr[(d * 4 + 1) * 64];
+        left = fr[(d * 4 + 2) * 64];
+        word = (uint32_t)fr[(d * 4 + 3) * 64];
+    }
+};
 #ifdef RAZ_WAVE_EMU
 #define RAZ_POOL_WAVES
 #else
@@ -521,6 +406,7 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
     // [(d * 4 + j) * 64 + lane] - instead of an HBM round trip in the middle of every node) and in E.pool_frames between launches
     __shared__ unsigned long long frames_lds[RAZ_SOLVER_MAX_DEPTH * 4 * 64];
     unsigned long long* fr = frames_lds + lane;                                                            // word j of level d: fr[(d * 4 + j) * 64]
+    const PoolFrames frames{fr};
     unsigned long long* fr_hbm = E.pool_frames + (size_t)w * RAZ_SOLVER_MAX_DEPTH * 4 * 64 + (size_t)lane;   // the same layout
     raz_solver_pool_hdr* ph = E.pool_hdr + part;
     const uint32_t nact = uni(ph->n_active);
@@ -528,10 +414,11 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
     const unsigned long long m1 = lw[3 * 64 + lane];
     bool have = (m1 & 1ULL) != 0;
     if (__ballot(have) == 0ULL && nact == 0u) return;   // nothing parked here, nothing to hand out
-    raz_bb own = lw[0 * 64 + lane], enemy = lw[1 * 64 + lane], left = lw[2 * 64 + lane];
-    int fresh = (int)((m1 >> 1) & 1ULL), flip = (int)((m1 >> 2) & 1ULL), task_sign = ((m1 >> 3) & 1ULL) ? -1 : 1;
+    SolverNode nd;   // the node the lane's search stands on
+    nd.own = lw[0 * 64 + lane]; nd.enemy = lw[1 * 64 + lane]; nd.left = lw[2 * 64 + lane];
+    nd.flip = (int)((m1 >> 2) & 1ULL); nd.bmv = (int)((m1 >> 16) & 0xffULL) - 1; nd.bsc = (int)((m1 >> 24) & 0xffULL) - 128; nd.pact = (int)((m1 >> 32) & 0xffULL) - 1;
+    int fresh = (int)((m1 >> 1) & 1ULL), task_sign = ((m1 >> 3) & 1ULL) ? -1 : 1, d = (int)((m1 >> 8) & 0xffULL);
     uint32_t exact = (uint32_t)((m1 >> 4) & 1ULL);
-    int d = (int)((m1 >> 8) & 0xffULL), bmv = (int)((m1 >> 16) & 0xffULL) - 1, bsc = (int)((m1 >> 24) & 0xffULL) - 128, pact = (int)((m1 >> 32) & 0xffULL) - 1;
     uint32_t g = (uint32_t)lw[4 * 64 + lane], gen = (uint32_t)(lw[4 * 64 + lane] >> 32);
     const unsigned long long m2 = lw[5 * 64 + lane];
     int task = (int)(m2 & 0xffffULL), task_n = (int)((m2 >> 16) & 0xffULL), task_ci = (int)((m2 >> 24) & 0xffULL), task_t = (int)((m2 >> 32) & 0xffffULL);
@@ -578,7 +465,7 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
         st_busy += 64u - (uint32_t)nidle;
         ++st_iters;
         bool hit = false;
-        int hit_m = 0, hit_s = 0;
+        int hit_s = 0;   // (the value is all a parent takes from a memo entry)
         const unsigned long long tk0 = prof_now();
         if ((iter & (RAZ_SOLVER_SLOW_EVERY - 1)) == 0) {
             // ---- 1. memo traffic goes out
@@ -588,7 +475,7 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
             raz_slot* pslot = nullptr;
             if (finding) {
                 const raz_slot* tab = E.memo + (size_t)g * E.M;
-                const uint32_t h = key_hash(own, enemy, 8u + exact);
+                const uint32_t h = key_hash(nd.own, nd.enemy, 8u + exact);
                 const raz_slot *s0 = tab + (h & (E.M - 1)), *s1 = tab + ((h + 1u) & (E.M - 1));
                 it0 = xk_load32(conc, &s0->idx_tag); it1 = xk_load32(conc, &s1->idx_tag);   // (memo entries cross between concurrent kernels: raz_engine_core.h xk_*)
                 b0 = xk_load64(conc, &s0->black); w0 = xk_load64(conc, &s0->white); b1 = xk_load64(conc, &s1->black); w1 = xk_load64(conc, &s1->white);
@@ -603,10 +490,10 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
             // tasks still leave in scan order (its `next` counter).  The list entry of a lane's next draw is requested one phase ahead
             if (!dry && nidle) {
                 bool got = false, saw_tasks = false;
-                // (RAZ_SOLVER_DRAW_GATE: of the lanes_per_solve lanes that walk to this solve, about as many draw as it has tasks left -
-                // a lane's turn comes round with its draws)
+                // (of the lanes_per_solve lanes that walk to this solve, about as many draw as it has tasks left - a lane's turn comes
+                // round with its draws)
                 const uint32_t every = peek_left ? (lanes_per_solve + peek_left - 1u) / peek_left : 0u;
-                const bool my_turn = !RAZ_SOLVER_DRAW_GATE || (every && (lane_id / nact + draws) % every == 0u);
+                const bool my_turn = every && (lane_id / nact + draws) % every == 0u;
                 if (!have) {
                     const uint32_t gg = next_solve;
                     saw_tasks = peek_left != 0u;
@@ -618,71 +505,51 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
                         peek_left = pn < pt ? pt - pn : 0u;
                     }
                     if (my_turn) {
-                    raz_solve_hdr* hh = solve_hdr(E, gg);
-                    const uint32_t t = atomicAdd(&hh->next, 1u);
-                    const uint32_t total = hh->total, window = hh->limit, ex = xk_load32(conc, &hh->exact), hgen = xk_load32(conc, &hh->gen);   // (fixed while the pool runs: requested beside the draw; exact and gen are the tree kernels' words)
-                    const int nt_ = t < total ? (int)solve_deep(E, gg)->sub_task[t] : 0;
-                    const bool beyond = RAZ_SOLVER_NE_WINDOW > 0 && t < total && (uint32_t)nt_ >= window;
-                    // A ticket outside this round's window (k_solve_scan's limit) goes back for the round that opens it - and so does one past
-                    // the end of the list: thousands of lanes draw at once, and a ticket that stayed drawn behind the window's end would be a
-                    // task nobody ever searches (first hardware run of the window: the batch did not finish; the emulator's waves draw one
-                    // after the other and never overshoot that far).  Tickets inside the window are handed out once each: the counter only
-                    // ever comes back down to the window's end (every subtraction undoes an addition that got a ticket >= that end).
-                    if (RAZ_SOLVER_NE_WINDOW > 0 && (beyond || t >= total)) atomicSub(&hh->next, 1u);   // (without a window a ticket past the end just stays drawn)
-                    if (t < total && !beyond) {
-                        got = true;
-                        SolverTree* T = solve_tree(E, gg);
-                        SolverDeep* D = solve_deep(E, gg);
-                        const int nt = nt_;   // the task's level-3 node
-                        const int te = T->task_entry[nt], n = te & 0xff, ci = te >> 8, hk = D->h_kind[nt], s0 = D->sub_first[nt];
-                        const raz_bb ho = D->h_own[nt], he = D->h_enemy[nt], hm = D->h_moves[nt];
-                        // (a task that has its result: dispatch restarted after the pool was re-partitioned; a node that is decided: moot)
-                        if (D->sub_result[t] == RAZ_SOLVER_UNKNOWN && !D->h_dead[nt]) {
-                            raz_bb no = ho, ne = he, nm = hm;
-                            int v = 0, kind = 2;   // an unsplit node: the search starts at the node itself (same mover: sign +)
-                            if (!(hk & 8)) {
-                                raz_bb m = hm;
-                                for (int j = s0; j < (int)t; ++j) m &= m - 1;
-                                kind = solver_play(__ffsll((long long)m) - 1, ho, he, no, ne, nm, v, ex != 0u);
-                            }
-                            int pm = 0, ps = 0;
-                            if (RAZ_SOLVER_PROBE_AT_DRAW && kind && bb_popcount(~(no | ne)) >= RAZ_SOLVER_LANE_MEMO_EMPTIES && memo_find_lane(E, gg, no, ne, ex, pm, ps)) {
-                                // the memo knows the subtree's root (a transposition another lane searched): the probe a search starts with,
-                                // made here, where the wave is waiting on memory anyway
-                                D->sub_result[t] = (signed char)((kind == 1 ? -1 : 1) * ps);
-                                ++st_done;
-                            } else if (kind) {
-                                g = gg;
-                                gen = hgen;
-                                exact = ex;
-                                task = (int)t;
-                                task_t = nt;
-                                task_n = n;
-                                task_ci = ci;
-                                task_sign = kind == 1 ? -1 : 1;
-                                d = 0;
-                                own = no;
-                                enemy = ne;
-                                left = nm;
-                                bmv = -1;
-                                bsc = -100;
-                                pact = -1;
-                                flip = 0;
-                                fresh = RAZ_SOLVER_PROBE_AT_DRAW ? 0 : 1;   // (its root was looked up in the memo just now)
-                                wait_find = false;
-                                have = true;
-                            } else {
-                                D->sub_result[t] = (signed char)v;
-                                ++st_done;
-                            }
-                        } else
-                            ++st_skipped;
-                    }
+                        raz_solve_hdr* hh = solve_hdr(E, gg);
+                        const uint32_t t = atomicAdd(&hh->next, 1u);   // (a ticket past the end just stays drawn)
+                        const uint32_t total = hh->total, ex = xk_load32(conc, &hh->exact), hgen = xk_load32(conc, &hh->gen);   // (fixed while the pool runs: requested beside the draw; exact and gen are the tree kernels' words)
+                        if (t < total) {
+                            got = true;
+                            SolverTree* T = solve_tree(E, gg);
+                            SolverDeep* D = solve_deep(E, gg);
+                            const int nt = D->sub_task[t];   // the task's level-3 node
+                            const int te = T->task_entry[nt], n = te & 0xff, ci = te >> 8, hk = D->h_kind[nt], s0 = D->sub_first[nt];
+                            const raz_bb ho = D->h_own[nt], he = D->h_enemy[nt], hm = D->h_moves[nt];
+                            // (a task that has its result: dispatch restarted after the pool was re-partitioned; a node that is decided: moot)
+                            if (D->sub_result[t] == RAZ_SOLVER_UNKNOWN && !D->h_dead[nt]) {
+                                raz_bb no = ho, ne = he, nm = hm;
+                                int v = 0, kind = 2;   // an unsplit node: the search starts at the node itself (same mover: sign +)
+                                if (!(hk & 8)) {
+                                    raz_bb m = hm;
+                                    for (int j = s0; j < (int)t; ++j) m &= m - 1;
+                                    kind = solver_play(__ffsll((long long)m) - 1, ho, he, no, ne, nm, v, ex != 0u);
+                                }
+                                if (kind) {
+                                    g = gg;
+                                    gen = hgen;
+                                    exact = ex;
+                                    task = (int)t;
+                                    task_t = nt;
+                                    task_n = n;
+                                    task_ci = ci;
+                                    task_sign = kind == 1 ? -1 : 1;
+                                    d = 0;
+                                    nd.begin(no, ne, nm);
+                                    fresh = 1;
+                                    wait_find = false;
+                                    have = true;
+                                } else {
+                                    D->sub_result[t] = (signed char)v;
+                                    ++st_done;
+                                }
+                            } else
+                                ++st_skipped;
+                        }
                     }
                 }
                 if (__ballot(got) == 0ULL) {
                     // (a phase in which lanes saw tasks but it was nobody's turn does not count: the tasks are still there)
-                    if (!(RAZ_SOLVER_DRAW_GATE && __ballot(!got && saw_tasks && !my_turn)) && ++empty_draws >= 2) dry = true;   // the listed solves have handed out everything (this launch)
+                    if (!__ballot(!got && saw_tasks && !my_turn) && ++empty_draws >= 2) dry = true;   // the listed solves have handed out everything (this launch)
                 } else
                     empty_draws = 0;
             }
@@ -691,11 +558,10 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
                 wait_find = false;
                 fresh = 0;   // (probed: a miss goes on with the node's moves)
                 uint32_t it = 0u;
-                if ((it0 >> 31) && b0 == own && w0 == enemy && ((it0 >> 30) & 1u) == exact) it = it0;
-                else if ((it0 >> 31) && (it1 >> 31) && b1 == own && w1 == enemy && ((it1 >> 30) & 1u) == exact) it = it1;
+                if ((it0 >> 31) && b0 == nd.own && w0 == nd.enemy && ((it0 >> 30) & 1u) == exact) it = it0;
+                else if ((it0 >> 31) && (it1 >> 31) && b1 == nd.own && w1 == nd.enemy && ((it1 >> 30) & 1u) == exact) it = it1;
                 if (it) {
                     hit = true;
-                    hit_m = (int)((it >> 8) & 0xffu) - 1;
                     hit_s = (int)(it & 0xffu) - 128;
                 }
             }
@@ -727,11 +593,10 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
             // at the next iteration without playing a move in this one (about one lane-iteration in 25).
             bool may_move = false;
             for (int returns = 0; returns <= RAZ_SOLVER_MAX_RETURNS; ++returns) {
-                const bool big = bb_popcount(~(own | enemy)) >= RAZ_SOLVER_LANE_MEMO_EMPTIES;
-                int rm = 0, rs = 0;
+                const bool big = bb_popcount(~(nd.own | nd.enemy)) >= RAZ_SOLVER_LANE_MEMO_EMPTIES;
+                int rs = 0;
                 bool done = false;
                 if (hit) {
-                    rm = hit_m;
                     rs = hit_s;
                     done = true;
                     hit = false;
@@ -741,16 +606,15 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
                     break;
                 } else {
                     fresh = 0;
-                    if (left == 0 || (!exact && bsc > 0)) {
+                    if (nd.finished(exact != 0u)) {
                         if (big) {   // remembered at the next slow phase (one finished node per lane at a time)
                             put_pending = true;
-                            put_own = own;
-                            put_enemy = enemy;
+                            put_own = nd.own;
+                            put_enemy = nd.enemy;
                             put_g = g;
-                            put_tag = 0x80000000u | (exact << 30) | ((uint32_t)(bmv + 1) << 8) | (uint32_t)(bsc + 128);
+                            put_tag = 0x80000000u | (exact << 30) | ((uint32_t)(nd.bmv + 1) << 8) | (uint32_t)(nd.bsc + 128);
                         }
-                        rm = bmv;
-                        rs = bsc;
+                        rs = nd.bsc;
                         done = true;
                     }
                 }
@@ -765,48 +629,10 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
                     ++st_done;
                     break;
                 }
-                // back to the parent
-                const int v = flip ? -rs : rs, a = pact;
-                --d;
-                own = fr[(d * 4 + 0) * 64];
-                enemy = fr[(d * 4 + 1) * 64];
-                left = fr[(d * 4 + 2) * 64];
-                const uint32_t meta = (uint32_t)fr[(d * 4 + 3) * 64];
-                bmv = (int)(meta & 0xffu) - 1;
-                bsc = (int)((meta >> 8) & 0xffu) - 128;
-                pact = (int)((meta >> 16) & 0xffu) - 1;
-                flip = (int)((meta >> 24) & 1u);
-                if (bsc < v) {
-                    bmv = a;
-                    bsc = v;
-                }
+                nd.give_to_parent(frames, d, rs);
             }
             tk_pop += prof_now() - tk1;
-            if (have && !wait_find && may_move) {
-                const int a = __ffsll((long long)left) - 1;
-                left &= left - 1;
-                raz_bb no, ne, nm;
-                int score;
-                const int kind = solver_play(a, own, enemy, no, ne, nm, score, exact != 0u);
-                if (kind) {   // down a ply
-                    fr[(d * 4 + 0) * 64] = own;
-                    fr[(d * 4 + 1) * 64] = enemy;
-                    fr[(d * 4 + 2) * 64] = left;
-                    fr[(d * 4 + 3) * 64] = (unsigned long long)((uint32_t)(bmv + 1) | ((uint32_t)(bsc + 128) << 8) | ((uint32_t)(pact + 1) << 16) | ((uint32_t)flip << 24));
-                    ++d;
-                    own = no;
-                    enemy = ne;
-                    left = nm;
-                    bmv = -1;
-                    bsc = -100;
-                    pact = a;
-                    flip = kind == 1 ? 1 : 0;
-                    fresh = 1;
-                } else if (bsc < score) {
-                    bmv = a;
-                    bsc = score;
-                }
-            }
+            if (have && !wait_find && may_move && nd.play_next(frames, d, exact != 0u)) fresh = 1;   // (down a ply: the child may be in the memo)
         }
     }
     {
@@ -825,12 +651,12 @@ __global__ __launch_bounds__(64) RAZ_POOL_WAVES void k_solve_run(raz_engine_dev 
     // park: the next launch goes on from here
     if (have)
         for (int i = 0; i < d * 4; ++i) fr_hbm[i * 64] = fr[i * 64];
-    lw[0 * 64 + lane] = own;
-    lw[1 * 64 + lane] = enemy;
-    lw[2 * 64 + lane] = left;
-    lw[3 * 64 + lane] = (have ? 1ULL : 0ULL) | ((unsigned long long)(fresh & 1) << 1) | ((unsigned long long)(flip & 1) << 2) | ((task_sign < 0 ? 1ULL : 0ULL) << 3) |
-                        ((unsigned long long)(exact & 1u) << 4) | ((wait_find ? 1ULL : 0ULL) << 5) | ((unsigned long long)(d & 0xff) << 8) | ((unsigned long long)((bmv + 1) & 0xff) << 16) |
-                        ((unsigned long long)((bsc + 128) & 0xff) << 24) | ((unsigned long long)((pact + 1) & 0xff) << 32);
+    lw[0 * 64 + lane] = nd.own;
+    lw[1 * 64 + lane] = nd.enemy;
+    lw[2 * 64 + lane] = nd.left;
+    lw[3 * 64 + lane] = (have ? 1ULL : 0ULL) | ((unsigned long long)(fresh & 1) << 1) | ((unsigned long long)(nd.flip & 1) << 2) | ((task_sign < 0 ? 1ULL : 0ULL) << 3) |
+                        ((unsigned long long)(exact & 1u) << 4) | ((wait_find ? 1ULL : 0ULL) << 5) | ((unsigned long long)(d & 0xff) << 8) | ((unsigned long long)((nd.bmv + 1) & 0xff) << 16) |
+                        ((unsigned long long)((nd.bsc + 128) & 0xff) << 24) | ((unsigned long long)((nd.pact + 1) & 0xff) << 32);
     lw[4 * 64 + lane] = (unsigned long long)g | ((unsigned long long)gen << 32);
     lw[5 * 64 + lane] = (unsigned long long)(task & 0xffff) | ((unsigned long long)(task_n & 0xff) << 16) | ((unsigned long long)(task_ci & 0xff) << 24) |
                         ((unsigned long long)(task_t & 0xffff) << 32);
@@ -863,10 +689,8 @@ __global__ __launch_bounds__(256) void k_solver_game_stats(raz_engine_dev E) {
 // result are skipped at the draw).  One thread per worker lane / per game.
 __global__ __launch_bounds__(256) void k_solve_pool_reset(raz_engine_dev E) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (size_t)E.W * 64) {
-        E.pool_state[(i / 64) * 1024 + 3 * 64 + (i % 64)] = 0ULL;
-        E.pool_state[(i / 64) * 1024 + 9 * 64 + (i % 64)] = 0ULL;
-    }
+    if (i < (size_t)E.W * 64)
+        E.pool_state[(i / 64) * 1024 + 3 * 64 + (i % 64)] = 0ULL;   // (word 3, bit 0: the lane has a search)
     if (i < E.B) {
         raz_solve_hdr* h = solve_hdr(E, (uint32_t)i);
         if (RAZ_SOLVE_STATE(h->state) == RAZ_SOLVE_RUNNING) {

@@ -16,24 +16,29 @@ from conftest import ROOT, _locked
 
 EMU_DIR = os.path.join(ROOT, "tests", "native", "wave_emu")
 EMU_LIB = os.path.join(ROOT, "tests", "native", "libraz_emu_solver.so")
+EMU_LIB_LAST2 = os.path.join(ROOT, "tests", "native", "libraz_emu_solver_last2.so")   # (the same kernels with -DRAZ_SOLVER_INLINE_LAST=2)
 
 
-@pytest.fixture(scope="module")
-def emu():
+def _build(out, extra=""):
     """The emulator's Makefile, untouched, run in a private COPY of its directory beside it (the same depth, so every relative path
     of the Makefile and of the sources still holds): its rule keeps intermediates (orc_*.o) beside itself and removes them at the
     end, so a build in the shared directory could take them from under another worker's build of another emulator library.
     (copytree keeps the time stamps: an up-to-date library is not rebuilt.)"""
     with _locked("emu_solver"), tempfile.TemporaryDirectory(prefix="wave_emu_solver.", dir=os.path.dirname(EMU_DIR)) as work:
         shutil.copytree(EMU_DIR, work, ignore=shutil.ignore_patterns("*.o", "_net", "_full"), dirs_exist_ok=True)
-        r = subprocess.run(["make", "-C", work, "OUT=../libraz_emu_solver.so", "KERNELS=$(CSRC)/raz_solver_batch.hip $(CSRC)/raz_capi.hip"],
-                           capture_output=True, text=True)
+        r = subprocess.run(["make", "-C", work, "OUT=../" + os.path.basename(out), "EXTRA=" + extra,
+                            "KERNELS=$(CSRC)/raz_solver_batch.hip $(CSRC)/raz_capi.hip"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     from reversi_alpha_zero_amd import _native as N
-    lib = ctypes.CDLL(EMU_LIB)
+    lib = ctypes.CDLL(out)
     for name in ("raz_last_error", "raz_solve_batch", "raz_solve_batch_workspace_bytes"):
         getattr(lib, name).restype, getattr(lib, name).argtypes = N.SIGNATURES[name]
     return lib
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return _build(EMU_LIB)
 
 
 def _aligned(nbytes):
@@ -106,6 +111,22 @@ def test_partition_independence(emu, exactly):
         got = solve(emu, cases, exactly, tuning=tuning, ws_bytes=ws_bytes)
         for a, b in zip(got, base):
             assert a.tobytes() == b.tobytes(), (hex(tuning), ws_bytes, exactly)
+
+
+def test_two_squares_finished_in_the_move_function(emu):
+    """RAZ_SOLVER_INLINE_LAST=2 (csrc/raz_solver_search.h: solver_play finishes positions of TWO empty squares with the reference's
+    loop and its non-exact stop) is the batch solver's option too, since it shares the pool's move function - k_sb_expand then makes
+    values of such children, in the call's mode (only a split down to a leaf size of 2 or 3 gets there).  The kernels built with
+    it, in a library of their own: the golden and random lists, and 65 rows of the mixed list as they come and split down to 2
+    empties, in both modes - equal to the yardsticks and byte-identical to the default build."""
+    last2 = _build(EMU_LIB_LAST2, "-DRAZ_SOLVER_INLINE_LAST=2")
+    runs = [(name, cases, 0) for name, cases in C.emu_lists().items()] + [("mixed", C.mixed_list(65), t) for t in (0, C.TUNE_LEAF(2))]
+    for exactly in (0, 1):
+        for name, cases, tuning in runs:
+            got, base = solve(last2, cases, exactly, tuning=tuning), solve(emu, cases, exactly, tuning=tuning)
+            C.assert_answers(got, cases, exactly, f"{name}, tuning {tuning:#x} (two squares in the move function)")
+            for a, b in zip(got, base):
+                assert a.tobytes() == b.tobytes(), (name, hex(tuning), exactly)
 
 
 def test_workspace_and_tuning_edges(emu):
