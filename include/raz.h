@@ -134,6 +134,11 @@ int raz_net_forward(const raz_net* net, const uint64_t* own, const uint64_t* ene
  *   RAZ_NET_FORM_WIDE             k_conv0_wide + k_conv3x3_wide + k_heads_wide (filters >= 128, % 64 == 0; reserved 0 or 2)
  *   RAZ_NET_FORM_F16X3_REPAIR     raznet-forward-v2 (reserved 4) with the in-forward repair of rows out of the f16 range
  *   RAZ_NET_FORM_F16X3_NO_REPAIR  raznet-forward-v2 without it (see raz_net_range_check)
+ *   RAZ_NET_FORM_F16_REPAIR       raznet-forward-v3 (reserved 8: the plain-f16 trunk, NOT within 1e-5 of the graph) on the shapes
+ *                                 where v2 repairs
+ *   RAZ_NET_FORM_F16_NO_REPAIR    raznet-forward-v3 on the shapes where v2 does not
+ * reserved 4 and 8 take filters % 128 == 0; on a shape k_net_mfma takes they answer RAZ_NET_FORM_MFMA like 0, on any other
+ * filters RAZ_EINVAL.
  * Negative (RAZ_EINVAL) for a NULL net or a `reserved` raz_net_forward refuses.  No device work. */
 #define RAZ_NET_FORM_MFMA 1
 #define RAZ_NET_FORM_MFMA_WAVE 2
@@ -142,6 +147,8 @@ int raz_net_forward(const raz_net* net, const uint64_t* own, const uint64_t* ene
 #define RAZ_NET_FORM_WIDE 5
 #define RAZ_NET_FORM_F16X3_REPAIR 6
 #define RAZ_NET_FORM_F16X3_NO_REPAIR 7
+#define RAZ_NET_FORM_F16_REPAIR 8
+#define RAZ_NET_FORM_F16_NO_REPAIR 9
 int raz_net_form(const raz_net* net, size_t n);
 
 /* raz_net.reserved selects the forward kernels: 0 = the exact-f32 kernels chosen by shape ("raznet-forward-v1": every output
@@ -153,7 +160,23 @@ int raz_net_form(const raz_net* net, size_t n);
  * is evaluated by the exact-f32 chains inside the same forward, and *overflowed = 1 reports that some forward since raz_net_load
  * had more such rows than it repairs (32; sticky).  On the other v2 shapes (RAZ_NET_FORM_F16X3_NO_REPAIR: filters >= 384, or
  * 256 with a wider value head) NO row is repaired: a single row out of range raises the sticky flag, that row's outputs cannot be
- * trusted, the other rows' can.  Either way: run the net with reserved = 0 once *overflowed = 1.  Synchronises `stream`. */
+ * trusted, the other rows' can.  Either way: run the net with reserved = 0 once *overflowed = 1.  Synchronises `stream`.
+ *
+ * 8 (filters % 128 == 0; opt-in, never chosen for the caller) = "raznet-forward-v3": v2 with every lo half taken as zero - the
+ * plain-f16 trunk, one f16 MFMA per product.  With h(x) = round-to-nearest-even of a float to f16 and S_l the per-layer power of
+ * two of v2's weight image (max |w| * S_l in [2^14, 2^15)):
+ *   stem             the exact-f32 chains of v1, then a = h(relu(.))
+ *   trunk layer l    out = h(relu(acc * (1 / S_l) + bias [+ skip])), acc = the f32 matrix-core accumulation of h(w * S_l) * a over
+ *                    all 9 * filters products (a product of two halfs is exact in f32); the skip operand is the stored f16 activation
+ *   heads            the exact-f32 chains of v1 on the f16 trunk output
+ * The only roundings are h() on weights and activations and the f32 accumulation: the outputs carry f16's error and are NOT
+ * within 1e-5 of the fp32 graph (measured: 1.2e-3 at the worst output of a trained 256x10 net where v2 is 2e-6; 1e-2
+ * on the sharp random nets of the tests).  Measured speed: 2.24 x v2's forward (11.6 against 25.9 ms for 8192 positions of the
+ * 256x10 net).  It is for callers who put noise on top of the net anyway (self-play data generation);
+ * evaluation against a reference stays on 0 or 4.  The weight image, the scratch size
+ * and the range contract are v2's: an activation >= 60000 flags its row, which is repaired by the exact-f32 chains on the
+ * RAZ_NET_FORM_F16_REPAIR shapes and raises the sticky flag on the RAZ_NET_FORM_F16_NO_REPAIR shapes, and a row's answer is a
+ * function of its position alone.  raz_net_range_check and raz_net_range_stats serve it unchanged. */
 int raz_net_range_check(const raz_net* net, int* overflowed, raz_stream_t stream);
 /* The same plus *rows_repaired: v2 rows (positions) since raz_net_load whose activations left the f16 range and were therefore
  * evaluated by the exact-f32 chains instead, inside the forward that met them (at most 32 rows per forward; a forward with more

@@ -36,7 +36,7 @@ size_t raz_net_f16x3_scratch_bytes(int F, size_t n);
 unsigned* raz_net_f16x3_flag(const float* W, int F, int R, int V);
 int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* own, const uint64_t* enemy,
                           const uint8_t* active, float* policy, float* value, size_t n, void* scratch, size_t scratch_bytes,
-                          hipStream_t s, const uint32_t* list, const uint32_t* n_ptr);
+                          hipStream_t s, const uint32_t* list, const uint32_t* n_ptr, bool split);
 int raz_net_forward_mfma(const float* W, int F, int R, int V, const uint64_t* own, const uint64_t* enemy,
                          const uint8_t* active, float* policy, float* value, size_t n, hipStream_t s,
                          unsigned long long* prof);
@@ -392,14 +392,14 @@ int raz_net_repair_rows(const float* W, int F, int R, int V, const uint64_t* own
     return raz_check_launch("raz_net_forward (range repair)");
 }
 
-// Engine-internal: raz_net_forward over a compacted batch (raz_leaf_cache.hip).  Only the f16x3 path has the indexed form;
+// Engine-internal: raz_net_forward over a compacted batch (raz_leaf_cache.hip).  Only the f16x3 path (v2 and v3) has the indexed form;
 // other nets run the ordinary forward over the rows whose `active` flag the cache left set.
 int raz_net_forward_compact(const raz_net* net, const uint64_t* own, const uint64_t* enemy, const uint8_t* active, float* policy,
                             float* value, size_t n, void* scratch, size_t scratch_bytes, hipStream_t stream, const uint32_t* list,
                             const uint32_t* n_ptr) {
-    if (n && net && f16x3_supported(net->filters) && net->reserved == 4)
+    if (n && net && f16x3_supported(net->filters) && (net->reserved == 4 || net->reserved == 8))
         return raz_net_forward_f16x3((const float*)net->d_weights, net->filters, net->res_layers, net->value_fc, own, enemy, active,
-                                     policy, value, n, scratch, scratch_bytes, stream, list, n_ptr);
+                                     policy, value, n, scratch, scratch_bytes, stream, list, n_ptr, net->reserved == 4);
     return raz_net_forward(net, own, enemy, active, policy, value, n, scratch, scratch_bytes, (raz_stream_t)stream);
 }
 
@@ -408,14 +408,17 @@ extern "C" int raz_net_form(const raz_net* net, size_t n) {
     (void)n;   // (no form depends on the batch size today)
     if (!net) return raz_fail(RAZ_EINVAL, "raz_net_form: NULL argument");
     const int F = net->filters, V = net->value_fc, rs = net->reserved;
-    if (rs != 0 && rs != 1 && rs != 2 && rs != 4)
-        return raz_fail(RAZ_EINVAL, "raz_net_forward: raz_net.reserved must be 0, 1, 2 or 4 (5 and 6 selected kernels that were removed in ABI 3)");
+    if (rs != 0 && rs != 1 && rs != 2 && rs != 4 && rs != 8)
+        return raz_fail(RAZ_EINVAL, "raz_net_forward: raz_net.reserved must be 0, 1, 2, 4 or 8 (5 and 6 selected kernels that were removed in ABI 3)");
     // reserved (tests): 1 forces the VALU kernel, 2 the one-wave-per-position MFMA kernel
     if (raz_net_mfma_supported(F, V) && rs != 1) return rs == 2 ? RAZ_NET_FORM_MFMA_WAVE : RAZ_NET_FORM_MFMA;
     // reserved 4: raznet-forward-v2 - the trunk on the f16 matrix cores with split operands (raz_net_f16x3.hip), within 1e-5
     // of the fp32 graph but not bit-identical to the exact-f32 kernels (0 / 5: raznet-forward-v1)
-    if (rs == 4) {
-        if (!f16x3_supported(F)) return raz_fail(RAZ_EINVAL, "raz_net_forward: the f16x3 kernel needs filters % 128 == 0");
+    // reserved 8: raznet-forward-v3 - the same trunk on the hi halfs alone (one matrix instruction per product): f16's own
+    // accuracy, NOT within 1e-5 of the graph (include/raz.h)
+    if (rs == 4 || rs == 8) {
+        if (!f16x3_supported(F)) return raz_fail(RAZ_EINVAL, "raz_net_forward: the f16x3 and f16 kernels (reserved 4, 8) need filters % 128 == 0");
+        if (rs == 8) return f16x3_repairs(F, V) ? RAZ_NET_FORM_F16_REPAIR : RAZ_NET_FORM_F16_NO_REPAIR;
         return f16x3_repairs(F, V) ? RAZ_NET_FORM_F16X3_REPAIR : RAZ_NET_FORM_F16X3_NO_REPAIR;
     }
     if (wide_supported(F) && rs != 1) return RAZ_NET_FORM_WIDE;
@@ -441,8 +444,10 @@ extern "C" int raz_net_forward(const raz_net* net, const uint64_t* own, const ui
         }
         case RAZ_NET_FORM_F16X3_REPAIR:
         case RAZ_NET_FORM_F16X3_NO_REPAIR:
+        case RAZ_NET_FORM_F16_REPAIR:
+        case RAZ_NET_FORM_F16_NO_REPAIR:
             return raz_net_forward_f16x3(W, F, net->res_layers, V, own, enemy, active, policy, value, n, scratch, scratch_bytes,
-                                         (hipStream_t)stream, nullptr, nullptr);
+                                         (hipStream_t)stream, nullptr, nullptr, form == RAZ_NET_FORM_F16X3_REPAIR || form == RAZ_NET_FORM_F16X3_NO_REPAIR);
         case RAZ_NET_FORM_WIDE:
             return raz_net_forward_wide(W, F, net->res_layers, V, own, enemy, active, policy, value, n, scratch, scratch_bytes,
                                         (hipStream_t)stream);

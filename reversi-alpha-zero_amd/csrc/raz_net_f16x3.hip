@@ -28,6 +28,12 @@
 //   LDS reads = ds_read_b128, conflict-free by construction: lanes 0-31 read consecutive 16-byte slots (squares or channels),
 //               lanes 32-63 the other k-group's plane; 0.5 reads per MFMA
 //   epilogue  = * 1/S, + bias, (+ skip), relu, split into (hi, lo), 8-byte stores that tile 512-byte runs
+//
+// "raznet-forward-v3" (SPLIT = false below; opt-in, raz_net.reserved = 8) is v2 with every lo half taken as zero: activations and
+// weights are the hi halfs alone, out = f16(relu(acc / S + bias [+ skip])) with ONE matrix instruction per product.  Same tiling,
+// LDS image, HBM layouts, weight image and scales; the lo planes in HBM and the lo halves of the LDS image are holes that v3 never
+// reads or writes (12 of a stage's 24 weight pieces and 2 of a chunk's 4 activation planes are moved).  Its error is f16's own
+// (about 11 bits per activation): NOT within 1e-5 of the fp32 graph - include/raz.h raz_net_range_check.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -104,6 +110,8 @@ constexpr int Z_OFF = NWAVE * ACT_POS;           // the zero rows inside an imag
 // Pipeline: stage s+1 (the next tap group's weights, and with the first tap group of a chunk that chunk's activations) is
 // in flight as LDS-DMA into the other buffer while stage s is computed; ONE barrier per stage (it also drains this wave's
 // share of the DMA issued a whole stage earlier).
+// SPLIT: true = raznet-forward-v2 (hi and lo halfs, three matrix instructions per product); false = v3 (hi halfs alone, one).
+template <bool SPLIT>
 __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* __restrict__ Wl, const float* __restrict__ bias,
                                                           const float* __restrict__ inv_scale_ptr, const unsigned char* in, unsigned char* out,
                                                           const unsigned char* skip, const uint8_t* __restrict__ active, int n, int F,
@@ -152,18 +160,26 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
     const unsigned char* wsrc = Wl + (size_t)ot * nchunks * 3 * W_STAGE + lane * 16;
     const unsigned char* asrc = in_pos + lane * 16;
     // stage `st` = (chunk st / 3, tap group st % 3): 24 weight pieces of 1 KiB (3 per wave) + with tap group 0 this wave's
-    // position's four activation planes of that chunk
+    // position's four activation planes of that chunk.  !SPLIT: the 12 hi pieces alone (piece p holds the hi halfs when p & 2 is
+    // clear: hi piece j is piece (j >> 1) * 4 + (j & 1); every wave moves hi piece wv, waves 0-3 also hi piece 8 + wv) and the two
+    // hi planes (0 and 2), to the places they have in the v2 image
     auto issue = [&](int c, int tg) {
         const int st = c * 3 + tg;
         const unsigned char* src = wsrc + (size_t)st * W_STAGE;
         unsigned char* dst = lds + LDS_W + (st & 1) * W_STAGE;
+        if constexpr (SPLIT) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) GLDS16(src + (wv * 3 + i) * 1024, dst + (wv * 3 + i) * 1024);
+            for (int i = 0; i < 3; ++i) GLDS16(src + (wv * 3 + i) * 1024, dst + (wv * 3 + i) * 1024);
+        } else {
+            const int p0w = (wv >> 1) * 4 + (wv & 1);
+            GLDS16(src + p0w * 1024, dst + p0w * 1024);
+            if (wv < 4) GLDS16(src + (p0w + 16) * 1024, dst + (p0w + 16) * 1024);   // hi piece 8 + wv = piece 16 + p0w
+        }
         if (tg == 0) {
             const unsigned char* a = asrc + (size_t)c * ACT_POS;
             unsigned char* ad = lds + LDS_ACT + (c & 1) * ACT_IMG + wv * ACT_POS;
 #pragma unroll
-            for (int pl = 0; pl < 4; ++pl) GLDS16(a + pl * 1024, ad + pl * 1024);
+            for (int pl = 0; pl < 4; pl += SPLIT ? 1 : 2) GLDS16(a + pl * 1024, ad + pl * 1024);
         }
     };
     issue(0, 0);
@@ -181,21 +197,33 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
 #pragma unroll
             for (int tt = 0; tt < 3; ++tt) {
                 const int t = tg * 3 + tt;
-                h8 bh[2], bl[2];
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    bh[nt] = *(const h8*)(lds + abase + boff[nt][t]);
-                    bl[nt] = *(const h8*)(lds + abase + boff[nt][t] + 1024);
-                }
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const h8 ah = *(const h8*)(lds + wbase + tt * 8192 + m * 512);
-                    const h8 al = *(const h8*)(lds + wbase + tt * 8192 + m * 512 + 2048);
+                if constexpr (SPLIT) {
+                    h8 bh[2], bl[2];
 #pragma unroll
                     for (int nt = 0; nt < 2; ++nt) {
-                        acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[nt], acc[m][nt], 0, 0, 0);
-                        acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[nt], acc[m][nt], 0, 0, 0);
-                        acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[nt], acc[m][nt], 0, 0, 0);
+                        bh[nt] = *(const h8*)(lds + abase + boff[nt][t]);
+                        bl[nt] = *(const h8*)(lds + abase + boff[nt][t] + 1024);
+                    }
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        const h8 ah = *(const h8*)(lds + wbase + tt * 8192 + m * 512);
+                        const h8 al = *(const h8*)(lds + wbase + tt * 8192 + m * 512 + 2048);
+#pragma unroll
+                        for (int nt = 0; nt < 2; ++nt) {
+                            acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[nt], acc[m][nt], 0, 0, 0);
+                            acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[nt], acc[m][nt], 0, 0, 0);
+                            acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[nt], acc[m][nt], 0, 0, 0);
+                        }
+                    }
+                } else {
+                    h8 bh[2];
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) bh[nt] = *(const h8*)(lds + abase + boff[nt][t]);
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        const h8 ah = *(const h8*)(lds + wbase + tt * 8192 + m * 512);
+#pragma unroll
+                        for (int nt = 0; nt < 2; ++nt) acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[nt], acc[m][nt], 0, 0, 0);
                     }
                 }
             }
@@ -222,9 +250,15 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = acc[m][nt][q * 4 + j] * inv_scale + bv[j];
                 if (skip_pos) {
-                    const h4 sh = *(const h4*)(skip_pos + o), sl = *(const h4*)(skip_pos + o + 1024);
+                    if constexpr (SPLIT) {
+                        const h4 sh = *(const h4*)(skip_pos + o), sl = *(const h4*)(skip_pos + o + 1024);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = v[j] + ((float)sh[j] + (float)sl[j]);
+                        for (int j = 0; j < 4; ++j) v[j] = v[j] + ((float)sh[j] + (float)sl[j]);
+                    } else {
+                        const h4 sh = *(const h4*)(skip_pos + o);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] = v[j] + (float)sh[j];
+                    }
                 }
                 h4 hi, lo;
 #pragma unroll
@@ -235,7 +269,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
                     lo[j] = (_Float16)(r - (float)hi[j]);
                 }
                 *(h4*)(out_pos + o) = hi;
-                *(h4*)(out_pos + o + 1024) = lo;
+                if constexpr (SPLIT) *(h4*)(out_pos + o + 1024) = lo;
             }
         }
     if (over) flag[(size_t)pos * RAZ_NET_ROWFLAG_WORDS] = 1u;   // an activation beyond the f16 range: this ROW is evaluated again by the exact-f32 kernel (raz_net_repair_rows)
@@ -244,7 +278,8 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
 
 // Layer 0: 2 bit planes -> F channels, exact f32 chains as in k_conv0_wide, written in the split layout.  The work per
 // position is tiny and latency-bound (scalar weight loads), so a position's 16-channel chunks are spread over the 4 waves
-// of a workgroup (lane = square, wave w takes chunks w, w + 4, ...).
+// of a workgroup (lane = square, wave w takes chunks w, w + 4, ...).  !SPLIT (v3): the hi planes alone are written.
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void k_conv0_split(const float* __restrict__ W0, const raz_bb* __restrict__ own,
                                                      const raz_bb* __restrict__ enemy, const uint8_t* __restrict__ active,
                                                      unsigned char* out, int n, int F, unsigned* __restrict__ flag,
@@ -297,13 +332,15 @@ __global__ __launch_bounds__(256) void k_conv0_split(const float* __restrict__ W
                 lo[j] = (_Float16)(r - (float)hi[j]);
             }
             *(h8*)(op + (size_t)ocb * ACT_POS + (g * 2 + 0) * 1024 + lane * 16) = hi;
-            *(h8*)(op + (size_t)ocb * ACT_POS + (g * 2 + 1) * 1024 + lane * 16) = lo;
+            if constexpr (SPLIT) *(h8*)(op + (size_t)ocb * ACT_POS + (g * 2 + 1) * 1024 + lane * 16) = lo;
         }
     }
     if (over) flag[(size_t)pos * RAZ_NET_ROWFLAG_WORDS] = 1u;
 }
 
-// Heads as in k_heads_wide (exact f32 chains), reading the trunk output in the split layout: x = hi + lo (exact in f32).
+// Heads as in k_heads_wide (exact f32 chains), reading the trunk output in the split layout: x = hi + lo (exact in f32);
+// !SPLIT (v3): x = hi, the lo planes are not read.
+template <bool SPLIT>
 __global__ __launch_bounds__(64) void k_heads_split(const float* __restrict__ H, const unsigned char* trunk,
                                                     const uint8_t* __restrict__ active, float* __restrict__ policy,
                                                     float* __restrict__ value, int n, int F, int V,
@@ -332,11 +369,12 @@ __global__ __launch_bounds__(64) void k_heads_split(const float* __restrict__ H,
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             const h8 hi = *(const h8*)(a + (size_t)c * ACT_POS + (g * 2 + 0) * 1024);
-            const h8 lo = *(const h8*)(a + (size_t)c * ACT_POS + (g * 2 + 1) * 1024);
+            h8 lo = hi;
+            if constexpr (SPLIT) lo = *(const h8*)(a + (size_t)c * ACT_POS + (g * 2 + 1) * 1024);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int ic = c * 16 + g * 8 + j;
-                const float xv = (float)hi[j] + (float)lo[j];
+                const float xv = SPLIT ? (float)hi[j] + (float)lo[j] : (float)hi[j];
                 p0 = fmaf(xv, pol_w[ic], p0);
                 p1 = fmaf(xv, pol_w[F + ic], p1);
                 v0 = fmaf(xv, val_w[ic], v0);
@@ -406,12 +444,17 @@ void raz_net_build_f16x3(const float* src, float* dst, int F, int R, int V) {
     }
 }
 
-// The heads over a trunk output in the split layout.
+// The heads over a trunk output in the split layout (split = false: over its hi planes alone, raznet-forward-v3).
+static int heads_launch(bool split, const float* W, int F, int R, int V, const unsigned char* trunk, const uint8_t* active, float* policy,
+                        float* value, size_t n, hipStream_t s, const uint32_t* list, const uint32_t* n_ptr) {
+    const auto heads = split ? k_heads_split<true> : k_heads_split<false>;
+    hipLaunchKernelGGL(heads, dim3((unsigned)n), dim3(64), (192 + (size_t)V) * sizeof(float), s,
+                       W + heads_off(F, R), trunk, active, policy, value, (int)n, F, V, list, n_ptr);
+    return raz_check_launch("raz_net_forward (split heads)");
+}
 int raz_net_heads_split(const float* W, int F, int R, int V, const unsigned char* trunk, const uint8_t* active, float* policy, float* value,
                         size_t n, hipStream_t s, const uint32_t* list, const uint32_t* n_ptr) {
-    hipLaunchKernelGGL(k_heads_split, dim3((unsigned)n), dim3(64), (192 + (size_t)V) * sizeof(float), s, W + heads_off(F, R), trunk, active,
-                       policy, value, (int)n, F, V, list, n_ptr);
-    return raz_check_launch("raz_net_forward (split heads)");
+    return heads_launch(true, W, F, R, V, trunk, active, policy, value, n, s, list, n_ptr);
 }
 
 // two activation buffers, then a 64-byte area per row for its range flag (raz_internal.h raz_net_repair_rows): linear in n
@@ -432,11 +475,12 @@ static int raz_net_flag_unrepaired(const unsigned* rowflag, unsigned* sticky, si
 // The sticky range flag lives in the device weight image, after the per-layer scales (raz_net_layout.h leaves 64 floats there).
 unsigned* raz_net_f16x3_flag(const float* W, int F, int R, int V) { return (unsigned*)(W + f16x3_scale_off(F, R, V) + (size_t)2 * R + 8); }
 
+// split: true = raznet-forward-v2, false = raznet-forward-v3 (the hi halfs alone; same scratch layout, the lo planes stay untouched).
 // list / n_ptr (both or neither; engine-internal, raz_leaf_cache.hip): evaluate only the exchange rows list[0 .. *n_ptr), packed
 // densely in the activation buffers - *n_ptr lives on the device, so every launch keeps its full grid and surplus blocks exit.
 int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* own, const uint64_t* enemy,
                           const uint8_t* active, float* policy, float* value, size_t n, void* scratch, size_t scratch_bytes,
-                          hipStream_t s, const uint32_t* list, const uint32_t* n_ptr) {
+                          hipStream_t s, const uint32_t* list, const uint32_t* n_ptr, bool split) {
     if (!scratch || scratch_bytes < raz_net_f16x3_scratch_bytes(F, n))
         return raz_fail(RAZ_ENOMEM, "raz_net_forward: scratch too small (raz_net_scratch_bytes)");
     unsigned char* bufA = (unsigned char*)scratch;
@@ -444,18 +488,19 @@ int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* o
     unsigned* sticky = raz_net_f16x3_flag(W, F, R, V);
     unsigned* flag = (unsigned*)(bufT + (size_t)n * F * 256);   // per-row range flags
     const float* scales = W + f16x3_scale_off(F, R, V);
-    const auto conv = k_conv3x3_f16x3;
-    {   // the kernel's LDS image exceeds the default dynamic limit: raise it once per device
-        static unsigned long long attr_devices = 0;   // bit d = done on device d (one process drives one device; a second one still gets its call)
+    const auto conv = split ? k_conv3x3_f16x3<true> : k_conv3x3_f16x3<false>;   // (v3 keeps v2's LDS image, lo halves unused)
+    {   // the kernel's LDS image exceeds the default dynamic limit: raise it once per device and kernel
+        static unsigned long long attr_devices[2] = {0, 0};   // [split] bit d = done on device d (one process drives one device; a second one still gets its call)
         int dev = 0;
         RAZ_HIP_TRY(hipGetDevice(&dev), "raz_net_forward: hipGetDevice");
-        if (dev >= 64 || !(attr_devices >> dev & 1)) {
+        if (dev >= 64 || !(attr_devices[split] >> dev & 1)) {
             RAZ_HIP_TRY(hipFuncSetAttribute((const void*)conv, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES), "raz_net_forward: hipFuncSetAttribute");
-            if (dev < 64) attr_devices |= 1ull << dev;
+            if (dev < 64) attr_devices[split] |= 1ull << dev;
         }
     }
     const unsigned conv_threads = NWAVE * 64;
-    hipLaunchKernelGGL(k_conv0_split, dim3((unsigned)n), dim3(256), 0, s, W + conv_off(F, 0), (const raz_bb*)own,
+    const auto conv0 = split ? k_conv0_split<true> : k_conv0_split<false>;
+    hipLaunchKernelGGL(conv0, dim3((unsigned)n), dim3(256), 0, s, W + conv_off(F, 0), (const raz_bb*)own,
                        (const raz_bb*)enemy, active, bufA, (int)n, F, flag, list, n_ptr);
     const unsigned groups = (unsigned)((n + NWAVE - 1) / NWAVE);
     const unsigned tiles = ((groups + 7) / 8) * 8 * (unsigned)(F / 128);
@@ -469,7 +514,7 @@ int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* o
                            (const unsigned char*)(W + f16x3_layer_off(F, R, V, l2)), W + conv_off(F, l2) + (size_t)F * 9 * F,
                            scales + (l2 - 1), (const unsigned char*)bufT, bufA, (const unsigned char*)bufA, list ? nullptr : active, (int)n, F, flag, n_ptr RAZ_STAMP_ARG);
     }
-    const int rc = raz_net_heads_split(W, F, R, V, bufA, active, policy, value, n, s, list, n_ptr);
+    const int rc = heads_launch(split, W, F, R, V, bufA, active, policy, value, n, s, list, n_ptr);
     if (rc != RAZ_OK) return rc;
     // rows whose activations left the f16 range: the same position through the exact-f32 chains (raznet-forward-v1), so a row's
     // answer is a function of its position alone - v2's when it stays in range, v1's when it does not

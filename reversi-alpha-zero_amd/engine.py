@@ -30,7 +30,8 @@ def _stream():
 
 
 # include/raz.h RAZ_NET_FORM_*
-FORMS = {1: "mfma", 2: "mfma_wave", 3: "wave_lds", 4: "wave_scratch", 5: "wide", 6: "f16x3_repair", 7: "f16x3_no_repair"}
+FORMS = {1: "mfma", 2: "mfma_wave", 3: "wave_lds", 4: "wave_scratch", 5: "wide", 6: "f16x3_repair", 7: "f16x3_no_repair",
+         8: "f16_repair", 9: "f16_no_repair"}
 
 
 class DeviceNet:
@@ -40,6 +41,10 @@ class DeviceNet:
         """kernel: None / "f32" = the exact-f32 kernels chosen by shape (raznet-forward-v1, bit-identical to the CPU oracle);
         "f16x3" = raznet-forward-v2 for filters % 128 == 0: the 3x3 trunk on the f16 matrix cores with split operands, within
         1e-5 of the fp32 graph (include/raz.h raz_net_range_check); "auto" = "f16x3" where supported, else "f32".
+        "f16" = raznet-forward-v3 for filters % 128 == 0, opt-in only ("auto" never picks it): the same trunk on plain f16 operands,
+        one matrix instruction per product instead of three.  The trade: a faster trunk for f16's own accuracy - activations and
+        weights rounded to 11 bits, outputs NOT within 1e-5 of the graph - which self-play under root noise tolerates and a
+        comparison against a reference does not.
         Test variants: "valu" = k_net_wave; "mfma_wave" = one single-wave workgroup per position."""
         import torch
         import struct
@@ -54,8 +59,9 @@ class DeviceNet:
         kernel = "valu" if force_valu_kernel else kernel
         if kernel == "auto":
             kernel = "f16x3" if (F >= 128 and F % 128 == 0) else "f32"
-        self.kernel_name = {None: "f32", "f32": "f32", "f16x3": "f16x3 split-operand MFMA trunk"}.get(kernel, kernel)
-        self.c.reserved = {None: 0, "f32": 0, "valu": 1, "mfma_wave": 2, "f16x3": 4}[kernel]
+        self.kernel_name = {None: "f32", "f32": "f32", "f16x3": "f16x3 split-operand MFMA trunk",
+                            "f16": "plain-f16 MFMA trunk (raznet-forward-v3)"}.get(kernel, kernel)
+        self.c.reserved = {None: 0, "f32": 0, "valu": 1, "mfma_wave": 2, "f16x3": 4, "f16": 8}[kernel]
         with torch.cuda.device(self.device):
             check(lib.raz_net_load(ctypes.byref(self.c), blob, len(blob), self._weights.data_ptr(), nbytes,
                                    _stream()), "raz_net_load")

@@ -256,7 +256,8 @@ class BatchedSelfPlayWorker:
         self.games_in_flight = games_in_flight
         self.block_games = block_games or games_in_flight
         # "auto": wide nets (filters % 128 == 0) run their trunk on the f16 matrix cores (raznet-forward-v2, within 1e-5 of
-        # the fp32 graph, 3.7x the exact-f32 kernels); "f32": the exact kernels everywhere (engine.DeviceNet)
+        # the fp32 graph, 3.7x the exact-f32 kernels); "f32": the exact kernels everywhere; "f16": opt-in, the trunk on plain f16
+        # operands (raznet-forward-v3: faster, f16's own accuracy - NOT within 1e-5 of the graph) (engine.DeviceNet)
         self.net_kernel = net_kernel
         # cross-game evaluation cache (include/raz.h raz_engine_set_leaf_cache): "auto" = 2^26 entries (21 GB) for wide nets,
         # whose forward is what a step costs; none for narrow nets (two extra launches per step cost more than they save)
@@ -800,13 +801,14 @@ class BatchedSelfPlayWorker:
         return blob if self.rank == 0 else t.cpu().numpy().tobytes()
 
     def _may_replay_block(self):
-        """True when a block may be discarded and played again - the net's trunk runs on the split-f16 kernels, whose range flag is
-        looked at after the block (run()): nothing of such a block may reach the disk before it is complete."""
+        """True when a block may be discarded and played again - the net's trunk runs on the f16 matrix cores (split operands, or
+        plain f16 with net_kernel="f16"), whose range flag is looked at after the block (run()): nothing of such a block may reach
+        the disk before it is complete."""
         if self._f32_fallback or self.net_kernel == "f32":
             return False
         import struct
         filters = struct.unpack_from("<5i", self.net_blob, 0)[2] if self.net_blob and len(self.net_blob) >= 20 else 256
-        return self.net_kernel in ("auto", "f16x3") and filters >= 128 and filters % 128 == 0
+        return self.net_kernel in ("auto", "f16x3", "f16") and filters >= 128 and filters % 128 == 0
 
     def _ids_per_block(self):
         """Consecutive game ids ONE rank plays between two gathers (_play_block)."""

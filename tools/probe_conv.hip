@@ -108,7 +108,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&dP, (size_t)nmax * F * 256));
     CK(hipFuncSetAttribute((const void*)k_conv3x3_wino, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
 #else
-    CK(hipFuncSetAttribute((const void*)k_conv3x3_f16x3, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+    CK(hipFuncSetAttribute((const void*)k_conv3x3_f16x3<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
 #endif
     hipStream_t s;
     CK(hipStreamCreate(&s));
@@ -124,7 +124,7 @@ int main(int argc, char** argv) {
                            (const uint8_t*)nullptr, n, F, dflag, (const uint32_t*)nullptr);
         (void)st;
 #else
-        hipLaunchKernelGGL(k_conv3x3_f16x3, dim3(tiles), dim3(NWAVE * 64), LDS_BYTES, s, W, dbias, dscale, in, dB, (const unsigned char*)nullptr,
+        hipLaunchKernelGGL(k_conv3x3_f16x3<true>, dim3(tiles), dim3(NWAVE * 64), LDS_BYTES, s, W, dbias, dscale, in, dB, (const unsigned char*)nullptr,
                            (const uint8_t*)nullptr, n, F, dflag, (const uint32_t*)nullptr, st);
 #endif
     };

@@ -177,7 +177,8 @@ def err_stats(a, b):
 
 
 def evaluate(net, blob, own, enemy, dev, chunk=8192, miopen_f64_sample=256):
-    """v1 / v2 kernels, fp32 torch (GPU) and the f64 graph on the given positions -> the error table."""
+    """v1 / v2 kernels, fp32 torch (GPU) and the f64 graph on the given positions -> the error table; v3 (the opt-in plain-f16
+    trunk, NOT a 1e-5 form) is measured beside them."""
     import torch
     from reversi_alpha_zero_amd.agent.model import ReversiNet
     from reversi_alpha_zero_amd.engine import DeviceNet
@@ -185,8 +186,9 @@ def evaluate(net, blob, own, enemy, dev, chunk=8192, miopen_f64_sample=256):
     torch.backends.cuda.matmul.allow_tf32 = False
     n32 = net.to(dev).eval()
     g64 = F64Graph(net, dev)
-    nets = {"v1_exact_f32": DeviceNet(blob, dev, kernel="f32"), "v2_split_f16": DeviceNet(blob, dev, kernel="f16x3")}
-    outs = {k: ([], []) for k in ("v1_exact_f32", "v2_split_f16", "torch_fp32", "f64")}
+    nets = {"v1_exact_f32": DeviceNet(blob, dev, kernel="f32"), "v2_split_f16": DeviceNet(blob, dev, kernel="f16x3"),
+            "v3_plain_f16": DeviceNet(blob, dev, kernel="f16")}
+    outs = {k: ([], []) for k in ("v1_exact_f32", "v2_split_f16", "v3_plain_f16", "torch_fp32", "f64")}
     t = {k: 0.0 for k in outs}
     for c0 in range(0, own.numel(), chunk):
         o, e = own[c0:c0 + chunk].contiguous(), enemy[c0:c0 + chunk].contiguous()
@@ -214,13 +216,15 @@ def evaluate(net, blob, own, enemy, dev, chunk=8192, miopen_f64_sample=256):
         outs["f64"][1].append(v)
     res = {k: (torch.cat(a), torch.cat(b)) for k, (a, b) in outs.items()}
     table = {}
-    for k in ("v1_exact_f32", "v2_split_f16", "torch_fp32"):
+    for k in ("v1_exact_f32", "v2_split_f16", "v3_plain_f16", "torch_fp32"):
         table[f"{k}_vs_f64"] = {"policy": err_stats(res[k][0], res["f64"][0]), "value": err_stats(res[k][1], res["f64"][1])}
     for k in ("v1_exact_f32", "v2_split_f16"):
         table[f"{k}_vs_torch_fp32"] = {"policy": err_stats(res[k][0], res["torch_fp32"][0]), "value": err_stats(res[k][1], res["torch_fp32"][1])}
     table["v2_vs_v1"] = {"policy": err_stats(res["v2_split_f16"][0], res["v1_exact_f32"][0]), "value": err_stats(res["v2_split_f16"][1], res["v1_exact_f32"][1])}
     ok, repaired = nets["v2_split_f16"].range_stats()
     table["v2_range_flag_clear"], table["v2_rows_repaired_on_the_exact_chains"] = bool(ok), int(repaired)
+    ok, repaired = nets["v3_plain_f16"].range_stats()
+    table["v3_range_flag_clear"], table["v3_rows_repaired_on_the_exact_chains"] = bool(ok), int(repaired)
     # the f64 restatement against torch's own f64 graph (MIOpen / rocBLAS f64) on a sample
     m = min(miopen_f64_sample, own.numel())
     n64 = ReversiNet(net.filters, net.res_layers, net.value_fc)
