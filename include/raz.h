@@ -493,6 +493,26 @@ int raz_engine_debug_read(raz_engine* e, int which, size_t offset, size_t bytes,
 #define RAZ_PROBE_ROOT_GAMMAS 15
 #define RAZ_PROBE_CHOICE 16
 int raz_spec_probe(int what, const void* in0, const void* in1, void* out, size_t n, raz_stream_t stream);
+/* Diagnostics: the evaluation cache's own claim / resolve / fill kernels (csrc/raz_leaf_cache.hip) on caller-supplied DEVICE buffers,
+ * with no engine and no net - the functions raz_engine_step calls around the net forward of one slice, so that a test can put
+ * positions no game reaches in front of them (equal tags with different keys, a full probe window, a window that wraps, claims left
+ * unfinished).  phase 0 clears the table as raz_engine_set_leaf_cache does; phase 1 is the half before the forward of rows
+ * [p0, p0 + pn) (claim, then resolve: hits are answered and leave `d_active`, in-batch duplicates leave it and wait, the rest are
+ * listed); phase 2 the half after it (fill: owners publish their answer, waiting rows copy their owner's).  `part` is the slice's
+ * number (its row count is n_compact[part]), `step` the value the engine's cache_step has for that step (it starts at 1: a cleared
+ * stamp never equals a live step).  max_discs: 0 = 64, as in raz_engine_set_leaf_cache.  d_own / d_enemy u64[rows], d_active
+ * u8[rows], d_policy f32[rows][64], d_value f32[rows].  Asynchronous on `stream`.
+ * d_cache: raz_leaf_cache_bytes(log2_entries, rows) bytes, 256-byte aligned.  Its sections, in this order, each rounded up to a
+ * multiple of 256 bytes (E = 2^log2_entries):
+ *   tags u64[E] (0 = empty, else the position's hash | 1), keys u64[E][2] (own, enemy), stamp u32[E], owner u32[E], ready u32[E],
+ *   pv f32[E][72] (policy 64, value, 7 words of padding), counters u64[8] ([0..3] as raz_engine_leaf_cache_stats),
+ *   n_compact u32[16], list u32[rows] (a slice's rows still to evaluate, RELATIVE to p0, from list[p0] on), role u32[rows]
+ *   (entry << 3 | kind; kind 0 none, 1 plain, 2 owner of the entry, 4 waiting for the entry's owner).
+ * RAZ_EINVAL and NO launch: an unknown phase, log2_entries outside 10..28, `bytes` below raz_leaf_cache_bytes, a NULL or misaligned
+ * buffer, p0 + pn > rows, part >= 16, pn == 0 in phase 1 or 2. */
+int raz_leaf_cache_probe(int phase, void* d_cache, size_t bytes, uint32_t log2_entries, uint32_t max_discs, size_t rows,
+                         const uint64_t* d_own, const uint64_t* d_enemy, uint8_t* d_active, float* d_policy, float* d_value,
+                         uint32_t p0, uint32_t pn, uint32_t part, uint32_t step, raz_stream_t stream);
 /* config.play.resign_threshold is mutated while the worker runs (worker/self_play.py:250-260: +-0.01 per 100
  * no-resign test games); moves decided from the next raz_engine_step on use the new value.  Trees, records and
  * random streams are untouched. */

@@ -133,6 +133,8 @@ SIGNATURES.update({
     "raz_engine_debug_read": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
     "raz_engine_set_resign_threshold": (c_int, [c_void_p, c_int, ctypes.c_double]),
     "raz_spec_probe": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "raz_leaf_cache_probe": (c_int, [c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_uint32, c_uint32, c_uint32, c_uint32, c_void_p]),
     "raz_solve_batch_workspace_bytes": (c_size_t, [c_size_t, c_int]),
     "raz_solve_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                         c_uint32, c_void_p]),

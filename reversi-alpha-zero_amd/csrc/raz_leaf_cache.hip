@@ -89,7 +89,9 @@ __global__ __launch_bounds__(256) void k_leaf_resolve(raz_leaf_cache_dev C, cons
     const uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= pn) return;
     const uint32_t r = p0 + j;
-    uint32_t role = C.role[r];
+    // All 64 lanes read the row's role, and lane 0 overwrites it below (HIT / WAIT / PLAIN).  The lanes meet here, so that every one
+    // has read the role before it is overwritten: true of a wave in lockstep anyway, and now of the wave emulator's lanes as well.
+    uint32_t role = __builtin_amdgcn_readfirstlane(C.role[r]);
     const uint32_t kind = role & 7u, i = role >> 3;
     if (kind == ROLE_NONE) return;
     if (kind == ROLE_FOLLOW) {
@@ -196,4 +198,34 @@ int raz_leaf_cache_before(const raz_leaf_cache_dev& c, const raz_engine_dev& d, 
 int raz_leaf_cache_after(const raz_leaf_cache_dev& c, const raz_engine_dev& d, uint32_t p0, uint32_t pn, uint32_t step, hipStream_t s) {
     hipLaunchKernelGGL(k_leaf_fill, dim3((pn + 3) / 4), dim3(256), 0, s, c, d.nn_policy, d.nn_value, p0, pn, step);
     return raz_check_launch("raz_engine_step: leaf cache fill");
+}
+
+// Diagnostics (include/raz.h): the three functions above on caller-supplied buffers, with no engine and no net.  Nothing is
+// re-implemented: a test sees the table the games see.
+extern "C" int raz_leaf_cache_probe(int phase, void* d_cache, size_t bytes, uint32_t log2_entries, uint32_t max_discs, size_t rows,
+                                    const uint64_t* d_own, const uint64_t* d_enemy, uint8_t* d_active, float* d_policy, float* d_value,
+                                    uint32_t p0, uint32_t pn, uint32_t part, uint32_t step, raz_stream_t stream) {
+    if (phase < 0 || phase > 2) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: unknown phase");
+    if (log2_entries < 10 || log2_entries > 28) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: log2_entries must be 10..28");
+    if (!d_cache || ((uintptr_t)d_cache & 255)) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: cache buffer NULL or not 256-byte aligned");
+    if (bytes < raz_leaf_cache_layout(log2_entries, rows, nullptr, nullptr)) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: buffer too small (raz_leaf_cache_bytes)");
+    if (!d_own || !d_enemy || !d_active || !d_policy || !d_value) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: NULL row buffer");
+    if (((uintptr_t)d_own & 7) || ((uintptr_t)d_enemy & 7) || ((uintptr_t)d_policy & 3) || ((uintptr_t)d_value & 3))
+        return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: misaligned row buffer");
+    if ((size_t)p0 + pn > rows) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: slice beyond the rows");
+    if (part >= 16) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: part must be below 16");
+    if (phase != 0 && pn == 0) return raz_fail(RAZ_EINVAL, "raz_leaf_cache_probe: empty slice");
+    raz_leaf_cache_dev c;
+    raz_leaf_cache_layout(log2_entries, rows, (unsigned char*)d_cache, &c);
+    c.max_discs = max_discs ? max_discs : 64u;
+    if (phase == 0) return raz_leaf_cache_clear(c, rows, (hipStream_t)stream);
+    raz_engine_dev d;
+    memset(&d, 0, sizeof d);
+    d.nn_own = (unsigned long long*)d_own;
+    d.nn_enemy = (unsigned long long*)d_enemy;
+    d.nn_active = d_active;
+    d.nn_policy = d_policy;
+    d.nn_value = d_value;
+    if (phase == 1) return raz_leaf_cache_before(c, d, p0, pn, part, step, (hipStream_t)stream);
+    return raz_leaf_cache_after(c, d, p0, pn, step, (hipStream_t)stream);
 }

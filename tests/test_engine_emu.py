@@ -257,6 +257,25 @@ def test_emulated_leaf_cache_changes_nothing(golden, blob):
     assert out[0] == out[1]
 
 
+def test_emulated_leaf_cache_with_a_disc_threshold_changes_nothing(golden, blob):
+    """leaf_cache_max_discs = 12: positions of more than 12 discs go past the table.  Games of the mini_shared variant equal the
+    run without a cache, some leaves are still served, and more rows are evaluated than with every position admitted.  (8 games
+    here; the 64-game form of this test runs on the device, tests/test_leaf_cache_gpu.py.)"""
+    cfg = config_of(_variant(golden, "mini_shared"))
+    out, st = [], []
+    for max_discs in (None, 12, 0):
+        eng = EmuEngine(cfg, blob, n_games=8, seed=7, sims_hint=4)
+        if max_discs is not None:
+            eng.attach_leaf_cache(14, max_discs)
+        eng.start(0, 4)
+        eng.run(chunk=64)
+        out.append(eng.records(save_policy_of_tau_1=False))
+        st.append(eng.leaf_cache_stats())
+    assert out[0] == out[1] == out[2]
+    assert st[0] == {"hits": 0, "in_batch_duplicates": 0, "evaluated": 0, "no_room": 0}
+    assert 0 < st[1]["hits"] and st[1]["evaluated"] > st[2]["evaluated"] and st[1]["no_room"] == 0, st
+
+
 @pytest.mark.parametrize("alpha", [1.3, 4.0])
 def test_emulated_dirichlet_alpha_above_one(golden, blob, alpha):
     """lib/bitboard.py:162-171 takes any alpha: above 1 numpy's legacy gamma sampler is Marsaglia-Tsang, restated on
