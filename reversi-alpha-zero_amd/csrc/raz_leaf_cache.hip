@@ -81,49 +81,87 @@ __global__ __launch_bounds__(256) void k_leaf_claim(raz_leaf_cache_dev C, const 
     C.role[r] = role;
 }
 
-// one wave per row (the answer of a hit is 65 floats)
+// A workgroup of 256 lanes takes 256 rows.  One lane per row decides the row's fate; the workgroup then counts its rows with
+// ballots and a prefix over its four waves, reserves its run of the compact list with ONE atomicAdd and adds to each counter
+// once (a returning atomic per row on one word was the whole run time of the one-wave-per-row form: 2 x 7.5 k of them on the
+// headline batch).  The answers of the hits (65 floats each) are copied last, a wave per hit row.  The order of the compact
+// list is the order of the workgroups' reservations: free, as it always was.
+constexpr uint32_t kResolveRows = 256;
+enum : uint32_t { FATE_NONE = 0, FATE_NET = 1, FATE_HIT = 2, FATE_WAIT = 3 };
+
 __global__ __launch_bounds__(256) void k_leaf_resolve(raz_leaf_cache_dev C, const unsigned long long* __restrict__ own,
                                                       const unsigned long long* __restrict__ enemy, uint8_t* __restrict__ active,
                                                       float* __restrict__ policy, float* __restrict__ value, uint32_t p0, uint32_t pn,
                                                       uint32_t part, uint32_t step) {
-    const uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (j >= pn) return;
-    const uint32_t r = p0 + j;
-    // All 64 lanes read the row's role, and lane 0 overwrites it below (HIT / WAIT / PLAIN).  The lanes meet here, so that every one
-    // has read the role before it is overwritten: true of a wave in lockstep anyway, and now of the wave emulator's lanes as well.
-    uint32_t role = __builtin_amdgcn_readfirstlane(C.role[r]);
-    const uint32_t kind = role & 7u, i = role >> 3;
-    if (kind == ROLE_NONE) return;
-    if (kind == ROLE_FOLLOW) {
-        const bool same = C.keys[2 * (size_t)i] == own[r] && C.keys[2 * (size_t)i + 1] == enemy[r];
-        const uint32_t ow = C.owner[i];
-        // Slices run concurrently on other streams and publish into the same table: the flag is read with ACQUIRE at agent
-        // scope (invalidates this CU's L1), so the answer read below cannot come from a line fetched before it was filled.
-        if (same && __hip_atomic_load(&C.ready[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {   // HIT
-            policy[(size_t)r * 64 + lane] = C.pv[(size_t)i * 72 + lane];
-            if (lane == 0) {
-                value[r] = C.pv[(size_t)i * 72 + 64];
+    __shared__ uint32_t s_count[4][3];           // per wave: rows for the net, hits, rows that wait for their owner
+    __shared__ uint32_t s_base;                  // where this workgroup's run of the compact list begins
+    __shared__ uint32_t s_hit_row[kResolveRows]; // the workgroup's hit rows (relative to its first row) and their entries
+    __shared__ uint32_t s_hit_entry[kResolveRows];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t j0 = blockIdx.x * kResolveRows, j = j0 + tid;
+    uint32_t fate = FATE_NONE, i = 0;
+    if (j < pn) {
+        const uint32_t r = p0 + j, role = C.role[r], kind = role & 7u;
+        i = role >> 3;
+        if (kind == ROLE_FOLLOW) {
+            const bool same = C.keys[2 * (size_t)i] == own[r] && C.keys[2 * (size_t)i + 1] == enemy[r];
+            const uint32_t ow = C.owner[i];
+            // Slices run concurrently on other streams and publish into the same table: the flag is read with ACQUIRE at agent
+            // scope (invalidates this CU's L1), so the answer read below - by a wave of this workgroup, after the barrier -
+            // cannot come from a line fetched before it was filled.
+            if (same && __hip_atomic_load(&C.ready[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {   // HIT
+                fate = FATE_HIT;
                 active[r] = 0;
                 C.role[r] = ROLE_NONE;
-                atomicAdd(&C.counters[0], 1ULL);
-            }
-            return;
-        }
-        if (same && C.stamp[i] == step && ow >= p0 && ow < p0 + pn && ow != r) {   // the owner is in this very batch
-            if (lane == 0) {
+            } else if (same && C.stamp[i] == step && ow >= p0 && ow < p0 + pn && ow != r) {   // the owner is in this very batch
+                fate = FATE_WAIT;
                 active[r] = 0;
                 C.role[r] = (i << 3) | ROLE_WAIT;
-                atomicAdd(&C.counters[1], 1ULL);
+            } else {   // tag collision, an entry of another slice or of an unfinished step: just evaluate it
+                fate = FATE_NET;
+                C.role[r] = ROLE_PLAIN;
             }
-            return;
+        } else if (kind != ROLE_NONE) {
+            fate = FATE_NET;
         }
-        role = ROLE_PLAIN;   // tag collision, an entry of another slice or of an unfinished step: just evaluate it
-        if (lane == 0) C.role[r] = ROLE_PLAIN;
     }
+    const unsigned long long m_net = __ballot(fate == FATE_NET), m_hit = __ballot(fate == FATE_HIT), m_wait = __ballot(fate == FATE_WAIT);
     if (lane == 0) {
-        const uint32_t ci = atomicAdd(&C.n_compact[part], 1u);
-        C.list[p0 + ci] = j;   // row index relative to the slice (the forward's pointers are offset by p0)
-        atomicAdd(&C.counters[2], 1ULL);
+        s_count[wv][0] = (uint32_t)__popcll(m_net);
+        s_count[wv][1] = (uint32_t)__popcll(m_hit);
+        s_count[wv][2] = (uint32_t)__popcll(m_wait);
+    }
+    __syncthreads();
+    uint32_t net_before = 0, hit_before = 0, n_net = 0, n_hit = 0, n_wait = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) {
+        if (w < wv) {
+            net_before += s_count[w][0];
+            hit_before += s_count[w][1];
+        }
+        n_net += s_count[w][0];
+        n_hit += s_count[w][1];
+        n_wait += s_count[w][2];
+    }
+    if (tid == 0) {
+        s_base = n_net ? atomicAdd(&C.n_compact[part], n_net) : 0u;
+        if (n_hit) atomicAdd(&C.counters[0], (unsigned long long)n_hit);
+        if (n_wait) atomicAdd(&C.counters[1], (unsigned long long)n_wait);
+        if (n_net) atomicAdd(&C.counters[2], (unsigned long long)n_net);
+    }
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+    if (fate == FATE_HIT) {
+        const uint32_t h = hit_before + (uint32_t)__popcll(m_hit & below);
+        s_hit_row[h] = tid;
+        s_hit_entry[h] = i;
+    }
+    __syncthreads();
+    if (fate == FATE_NET)   // row index relative to the slice (the forward's pointers are offset by p0)
+        C.list[p0 + s_base + net_before + (uint32_t)__popcll(m_net & below)] = j;
+    for (uint32_t h = wv; h < n_hit; h += 4) {
+        const size_t r = (size_t)p0 + j0 + s_hit_row[h], e = s_hit_entry[h];
+        policy[r * 64 + lane] = C.pv[e * 72 + lane];
+        if (lane == 0) value[r] = C.pv[e * 72 + 64];
     }
 }
 
@@ -190,7 +228,7 @@ int raz_leaf_cache_clear(const raz_leaf_cache_dev& c, size_t rows, hipStream_t s
 int raz_leaf_cache_before(const raz_leaf_cache_dev& c, const raz_engine_dev& d, uint32_t p0, uint32_t pn, uint32_t part, uint32_t step,
                           hipStream_t s) {
     hipLaunchKernelGGL(k_leaf_claim, dim3((pn + 255) / 256), dim3(256), 0, s, c, d.nn_own, d.nn_enemy, d.nn_active, p0, pn, part, step);
-    hipLaunchKernelGGL(k_leaf_resolve, dim3((pn + 3) / 4), dim3(256), 0, s, c, d.nn_own, d.nn_enemy, d.nn_active, d.nn_policy, d.nn_value,
+    hipLaunchKernelGGL(k_leaf_resolve, dim3((pn + kResolveRows - 1) / kResolveRows), dim3(256), 0, s, c, d.nn_own, d.nn_enemy, d.nn_active, d.nn_policy, d.nn_value,
                        p0, pn, part, step);
     return raz_check_launch("raz_engine_step: leaf cache lookup");
 }

@@ -27,7 +27,8 @@
 //               zero row in the same bank class, so there are no predicates and no halo in the image
 //   LDS reads = ds_read_b128, conflict-free by construction: lanes 0-31 read consecutive 16-byte slots (squares or channels),
 //               lanes 32-63 the other k-group's plane; 0.5 reads per MFMA
-//   epilogue  = * 1/S, + bias, (+ skip), relu, split into (hi, lo), 8-byte stores that tile 512-byte runs
+//   epilogue  = the wave's halves trade accumulators so that a lane owns the 8 channels of one square; * 1/S, + bias, (+ skip),
+//               relu, split into (hi, lo), 16-byte stores: a wave writes whole 1 KiB planes
 //
 // "raznet-forward-v3" (SPLIT = false below; opt-in, raz_net.reserved = 8) is v2 with every lo half taken as zero: activations and
 // weights are the hi halfs alone, out = f16(relu(acc / S + bias [+ skip])) with ONE matrix instruction per product.  Same tiling,
@@ -101,6 +102,25 @@ constexpr int Z_OFF = NWAVE * ACT_POS;           // the zero rows inside an imag
 #define RAZ_STAMP_AT(i_)
 #define RAZ_STAMP_END
 #endif
+
+// The two halves of a wave trade one value each: lane l < 32 gives `b` to lane l + 32 and takes that lane's `a`.  Afterwards
+// `first` holds (a of lane l, b of lane l - 32) and `second` (a of lane l + 32, b of lane l) in lanes (< 32, >= 32).  On the device
+// this is ONE v_permlane32_swap_b32; the wave emulator has no such builtin and says the same with a shuffle.  The shuffle form on
+// the device (ds_bpermute and three selects per value, 128 values per lane in the conv epilogue) was measured against it: the
+// epilogue takes 12.8 k instead of 11.5 k cycles (profiles/r8/conv_f16x3_epilogue_trade_shuffle_vs_swap.json).  Pure data movement
+// either way; tests/test_net_f16x3_bits_gpu.py holds the device form to the bits recorded before it existed.
+__device__ __forceinline__ void halves_trade(float a, float b, int upper, float& first, float& second) {
+#ifdef RAZ_WAVE_EMU
+    const float got = __shfl_xor(upper ? a : b, 32);
+    first = upper ? got : a;
+    second = upper ? b : got;
+#else
+    (void)upper;
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    first = __uint_as_float(r[0]);
+    second = __uint_as_float(r[1]);
+#endif
+}
 
 #define GLDS16(gptr, lptr)                                                                                      \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),                     \
@@ -232,110 +252,167 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
     RAZ_STAMP_AT(2);
     if (!live) return;
     const float inv_scale = *inv_scale_ptr;
-    // epilogue.  D layout: column = lane & 31 = square, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel in the 32-tile
-    unsigned char* out_pos = out + (size_t)pos * pos_bytes;
-    const unsigned char* skip_pos = skip ? skip + (size_t)pos * pos_bytes : nullptr;
-    bool over = false;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
+    // epilogue.  D layout: column = lane & 31 = square inside tile nt, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel in the
+    // 32-tile: a lane holds channels 4 kg .. 4 kg + 3 of every 8-channel group, for the squares lane & 31 and 32 + (lane & 31).  The
+    // halves of the wave trade (halves_trade): afterwards lane l holds all 8 channels of square l, one whole 16-byte unit of the
+    // layout per plane, so a wave reads and writes lane-linear 1 KiB planes.  The arithmetic per element is what it always was.
+    unsigned char* out_pos = out + (size_t)pos * pos_bytes + lane * 16;
+    const unsigned char* skip_pos = skip ? skip + (size_t)pos * pos_bytes + lane * 16 : nullptr;
+    // the skip rows of the 32-tile m + 1 are asked for before tile m is computed (out may BE skip: a lane reads exactly the
+    // 16 bytes it overwrites later, so the loads may run ahead of the stores of other units)
+    h8 skh[2][4], skl[2][4];
+    auto load_skip = [&](int m) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int oc8 = ot * OCT + m * 32 + q * 8;   // this lane pair's 8-channel group; this lane holds 4 of them
-            const f32x4 bv = *(const f32x4*)(bias + oc8 + 4 * kg);
+            const int oc8 = ot * OCT + m * 32 + q * 8;
             const size_t unit = (size_t)(oc8 >> 4) * ACT_POS + (size_t)((oc8 >> 3) & 1) * 2048;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                const size_t o = unit + (size_t)(nt * 32 + (lane & 31)) * 16 + kg * 8;
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = acc[m][nt][q * 4 + j] * inv_scale + bv[j];
-                if (skip_pos) {
-                    if constexpr (SPLIT) {
-                        const h4 sh = *(const h4*)(skip_pos + o), sl = *(const h4*)(skip_pos + o + 1024);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = v[j] + ((float)sh[j] + (float)sl[j]);
-                    } else {
-                        const h4 sh = *(const h4*)(skip_pos + o);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = v[j] + (float)sh[j];
-                    }
-                }
-                h4 hi, lo;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float r = v[j] > 0.0f ? v[j] : 0.0f;
-                    over |= !(r < 60000.0f);
-                    hi[j] = (_Float16)r;
-                    lo[j] = (_Float16)(r - (float)hi[j]);
-                }
-                *(h4*)(out_pos + o) = hi;
-                if constexpr (SPLIT) *(h4*)(out_pos + o + 1024) = lo;
-            }
+            skh[m & 1][q] = *(const h8*)(skip_pos + unit);
+            if constexpr (SPLIT) skl[m & 1][q] = *(const h8*)(skip_pos + unit + 1024);
         }
+    };
+    if (skip_pos) load_skip(0);
+    bool over = false;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        if (skip_pos && m + 1 < 4) load_skip(m + 1);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int oc8 = ot * OCT + m * 32 + q * 8;   // this lane's 8-channel group (wave-uniform: the bias comes by scalar loads)
+            const size_t unit = (size_t)(oc8 >> 4) * ACT_POS + (size_t)((oc8 >> 3) & 1) * 2048;
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) halves_trade(acc[m][0][q * 4 + j], acc[m][1][q * 4 + j], kg, v[j], v[4 + j]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = v[j] * inv_scale + bias[oc8 + j];
+            if (skip_pos) {
+                const h8 sh = skh[m & 1][q];
+                if constexpr (SPLIT) {
+                    const h8 sl = skl[m & 1][q];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = v[j] + ((float)sh[j] + (float)sl[j]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = v[j] + (float)sh[j];
+                }
+            }
+            h8 hi, lo;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float r = v[j] > 0.0f ? v[j] : 0.0f;
+                over |= !(r < 60000.0f);
+                hi[j] = (_Float16)r;
+                lo[j] = (_Float16)(r - (float)hi[j]);
+            }
+            *(h8*)(out_pos + unit) = hi;
+            if constexpr (SPLIT) *(h8*)(out_pos + unit + 1024) = lo;
+        }
+    }
     if (over) flag[(size_t)pos * RAZ_NET_ROWFLAG_WORDS] = 1u;   // an activation beyond the f16 range: this ROW is evaluated again by the exact-f32 kernel (raz_net_repair_rows)
     RAZ_STAMP_END;
 }
 
-// Layer 0: 2 bit planes -> F channels, exact f32 chains as in k_conv0_wide, written in the split layout.  The work per
-// position is tiny and latency-bound (scalar weight loads), so a position's 16-channel chunks are spread over the 4 waves
-// of a workgroup (lane = square, wave w takes chunks w, w + 4, ...).  !SPLIT (v3): the hi planes alone are written.
+// Layer 0: 2 bit planes -> F channels, exact f32 chains as in k_conv0_wide (per output: acc = bias; for each tap fmaf(x0, w, acc)
+// then fmaf(x1, w, acc)), written in the split layout.  A workgroup takes TWO rows (2 b and 2 b + 1); lane = square; the 16-channel
+// chunks are spread over its 4 waves (wave w takes chunks w, w + 4, ...).  A lane carries the same output channel of both rows as
+// one register pair, so a chain step is one v_pk_fma_f32 whose weight is a scalar register read by both halves: the weights reach
+// the lanes by scalar loads, each fetched once for two rows.  8 output channels (one 16-byte unit per plane and row) are live at a
+// time: under 80 VGPRs, so a SIMD holds 6 waves, and they hide the scalar loads and the store drain of one another - the kernel
+// writes F * 256 bytes per row and is otherwise idle.  The fully unrolled 16 x 18 form before it took 256 VGPRs and spilled
+// its weights: one wave per SIMD, every latency exposed.  !SPLIT (v3): the hi planes alone are written.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr int CONV0_ROWS = 2;   // rows per workgroup
+
 template <bool SPLIT>
-__global__ __launch_bounds__(256) void k_conv0_split(const float* __restrict__ W0, const raz_bb* __restrict__ own,
-                                                     const raz_bb* __restrict__ enemy, const uint8_t* __restrict__ active,
-                                                     unsigned char* out, int n, int F, unsigned* __restrict__ flag,
-                                                     const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_ptr) {
-    const int pos = blockIdx.x, lane = threadIdx.x & 63;
+__global__ __launch_bounds__(256, 6) void k_conv0_split(const float* __restrict__ W0, const raz_bb* __restrict__ own,
+                                                        const raz_bb* __restrict__ enemy, const uint8_t* __restrict__ active,
+                                                        unsigned char* out, int n, int F, unsigned* __restrict__ flag,
+                                                        const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_ptr) {
+    const int posA = blockIdx.x * CONV0_ROWS, posB = posA + 1, lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the weight reads below stay scalar loads
     // the forward's first kernel clears the per-row range flags (word 0 of every row's area) and the repair counter (word 1 of row 0's)
     if (threadIdx.x == 0) {
-        flag[(size_t)pos * RAZ_NET_ROWFLAG_WORDS] = 0u;
-        if (pos == 0) flag[1] = 0u;
+        flag[(size_t)posA * RAZ_NET_ROWFLAG_WORDS] = 0u;
+        if (posB < n) flag[(size_t)posB * RAZ_NET_ROWFLAG_WORDS] = 0u;
+        if (posA == 0) flag[1] = 0u;
     }
     __syncthreads();
     if (n_ptr) n = (int)*n_ptr < n ? (int)*n_ptr : n;
-    if (pos >= n || (!list && active && !active[pos])) return;
-    bool over = false;
-    const size_t src = list ? list[pos] : (size_t)pos;   // compacted batch: row `pos` holds the leaf of exchange row list[pos]
-    const raz_bb bo = own[src], be = enemy[src];
+    const bool liveA = posA < n && (list || !active || active[posA]);
+    const bool liveB = posB < n && (list || !active || active[posB]);
+    if (!liveA && !liveB) return;
+    // compacted batch: row `pos` holds the leaf of exchange row list[pos].  A row that is not live computes on an empty board and stores nothing
+    raz_bb bo[2] = {0, 0}, be[2] = {0, 0};
+    if (liveA) {
+        const size_t src = list ? list[posA] : (size_t)posA;
+        bo[0] = own[src];
+        be[0] = enemy[src];
+    }
+    if (liveB) {
+        const size_t src = list ? list[posB] : (size_t)posB;
+        bo[1] = own[src];
+        be[1] = enemy[src];
+    }
     const int y = lane >> 3, x = lane & 7;
-    float x0[9], x1[9];
+    f32x2 x0[9], x1[9];   // (row A, row B)
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
         const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
         const bool ok = (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
         const int s = (yy * 8 + xx) & 63;
-        x0[t] = ok ? (float)((bo >> s) & 1) : 0.0f;
-        x1[t] = ok ? (float)((be >> s) & 1) : 0.0f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            x0[t][k] = ok ? (float)(uint32_t)((bo[k] >> s) & 1) : 0.0f;
+            x1[t][k] = ok ? (float)(uint32_t)((be[k] >> s) & 1) : 0.0f;
+        }
     }
     const float* bias = W0 + (size_t)F * 18;
-    unsigned char* op = out + (size_t)pos * F * 256;
+    unsigned char* op = out + (size_t)posA * F * 256 + lane * 16;   // row B: + F * 256
+    bool overA = false, overB = false;
     for (int ocb = wv; ocb < F / 16; ocb += 4) {
-        float acc[16];
+#pragma unroll 1
+        for (int g = 0; g < 2; ++g) {   // the chunk's two 8-channel groups
+            f32x2 acc[8];
 #pragma unroll
-        for (int o = 0; o < 16; ++o) acc[o] = bias[ocb * 16 + o];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const float* wt = W0 + ((size_t)ocb * 9 + t) * 32;
-#pragma unroll
-            for (int o = 0; o < 16; ++o) acc[o] = fmaf(x0[t], wt[o], acc[o]);
-#pragma unroll
-            for (int o = 0; o < 16; ++o) acc[o] = fmaf(x1[t], wt[16 + o], acc[o]);
-        }
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            h8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float r = acc[g * 8 + j] > 0.0f ? acc[g * 8 + j] : 0.0f;
-                over |= !(r < 60000.0f);
-                hi[j] = (_Float16)r;
-                lo[j] = (_Float16)(r - (float)hi[j]);
+            for (int o = 0; o < 8; ++o) {
+                const float b = bias[ocb * 16 + g * 8 + o];
+                acc[o] = (f32x2){b, b};
             }
-            *(h8*)(op + (size_t)ocb * ACT_POS + (g * 2 + 0) * 1024 + lane * 16) = hi;
-            if constexpr (SPLIT) *(h8*)(op + (size_t)ocb * ACT_POS + (g * 2 + 1) * 1024 + lane * 16) = lo;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const float* wt = W0 + ((size_t)ocb * 9 + t) * 32 + g * 8;
+#pragma unroll
+                for (int o = 0; o < 8; ++o) {
+                    const float w = wt[o];
+                    acc[o] = __builtin_elementwise_fma(x0[t], (f32x2){w, w}, acc[o]);
+                }
+#pragma unroll
+                for (int o = 0; o < 8; ++o) {
+                    const float w = wt[16 + o];
+                    acc[o] = __builtin_elementwise_fma(x1[t], (f32x2){w, w}, acc[o]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (!(k ? liveB : liveA)) continue;
+                h8 hi, lo;
+                bool over = false;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float r = acc[j][k] > 0.0f ? acc[j][k] : 0.0f;
+                    over |= !(r < 60000.0f);
+                    hi[j] = (_Float16)r;
+                    lo[j] = (_Float16)(r - (float)hi[j]);
+                }
+                if (k) overB |= over;
+                else overA |= over;
+                unsigned char* o16 = op + (size_t)k * F * 256 + (size_t)ocb * ACT_POS + (g * 2) * 1024;
+                *(h8*)o16 = hi;
+                if constexpr (SPLIT) *(h8*)(o16 + 1024) = lo;
+            }
         }
     }
-    if (over) flag[(size_t)pos * RAZ_NET_ROWFLAG_WORDS] = 1u;
+    if (overA) flag[(size_t)posA * RAZ_NET_ROWFLAG_WORDS] = 1u;
+    if (overB) flag[(size_t)posB * RAZ_NET_ROWFLAG_WORDS] = 1u;
 }
 
 // Heads as in k_heads_wide (exact f32 chains), reading the trunk output in the split layout: x = hi + lo (exact in f32);
@@ -500,7 +577,7 @@ int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* o
     }
     const unsigned conv_threads = NWAVE * 64;
     const auto conv0 = split ? k_conv0_split<true> : k_conv0_split<false>;
-    hipLaunchKernelGGL(conv0, dim3((unsigned)n), dim3(256), 0, s, W + conv_off(F, 0), (const raz_bb*)own,
+    hipLaunchKernelGGL(conv0, dim3((unsigned)((n + CONV0_ROWS - 1) / CONV0_ROWS)), dim3(256), 0, s, W + conv_off(F, 0), (const raz_bb*)own,
                        (const raz_bb*)enemy, active, bufA, (int)n, F, flag, list, n_ptr);
     const unsigned groups = (unsigned)((n + NWAVE - 1) / NWAVE);
     const unsigned tiles = ((groups + 7) / 8) * 8 * (unsigned)(F / 128);

@@ -6,7 +6,8 @@
 //            position counts (tile-round quantisation: 2 x ceil(n / 8) tiles over 256 CUs)
 //   stamps   one launch with per-wave timestamps: where a workgroup's time goes (start-up until stage 0 has landed, K loop,
 //            barrier wait inside the loop, epilogue, store drain), the gap a CU shows between two consecutive workgroups, the
-//            shader clock (s_memtime ticks per s_memrealtime tick at 100 MHz)
+//            shader clock (s_memtime ticks per s_memrealtime tick at 100 MHz); `stamps <reps> skip` adds the skip path
+//            (out == skip, as in a residual block's second convolution)
 // Build (cross-compiles without a GPU):  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/probe_conv.hip -o tools/probe_conv
 // -DPROBE_WINO builds tools/probe_wino instead: the same `time` / `pmc` experiments on k_conv3x3_wino (the Winograd experiment,
 // tools/experiments/raz_net_wino.hip: 4 positions x 128 output channels per workgroup, transformed activations in and out).
@@ -66,6 +67,9 @@ int main(int argc, char** argv) {
     const int F = 256;
     int nmax = 8192, reps = 20;
     const char* mode = argc > 1 ? argv[1] : "all";
+    // `stamps <reps> skip`: the form of a residual block's second convolution - the skip rows are read from the buffer the output
+    // goes to (the few launches of the experiment add up in place; the values stay O(1))
+    const bool with_skip = argc > 3 && !strcmp(mode, "stamps") && !strcmp(argv[3], "skip");
     if (argc > 2) reps = atoi(argv[2]);
     const size_t pos_bytes = (size_t)F * IN_BYTES_PER_F;
     const size_t wl_bytes = (size_t)F * F * W_TAPS * 4;
@@ -102,6 +106,7 @@ int main(int argc, char** argv) {
         const float sc = 1.0f / 32768.f / 2304.f;   // keeps the outputs O(1): no range flag
         CK(hipMemcpy(dscale, &sc, 4, hipMemcpyHostToDevice));
         CK(hipMemset(dflag, 0, (size_t)nmax * 64 + 64));
+        CK(hipMemset(dB, 0, nmax * pos_bytes));   // (read as the skip rows by `stamps <reps> skip`)
     }
 #ifdef PROBE_WINO
     unsigned char* dP;
@@ -124,8 +129,8 @@ int main(int argc, char** argv) {
                            (const uint8_t*)nullptr, n, F, dflag, (const uint32_t*)nullptr);
         (void)st;
 #else
-        hipLaunchKernelGGL(k_conv3x3_f16x3<true>, dim3(tiles), dim3(NWAVE * 64), LDS_BYTES, s, W, dbias, dscale, in, dB, (const unsigned char*)nullptr,
-                           (const uint8_t*)nullptr, n, F, dflag, (const uint32_t*)nullptr, st);
+        hipLaunchKernelGGL(k_conv3x3_f16x3<true>, dim3(tiles), dim3(NWAVE * 64), LDS_BYTES, s, W, dbias, dscale, in, dB,
+                           with_skip ? (const unsigned char*)dB : (const unsigned char*)nullptr, (const uint8_t*)nullptr, n, F, dflag, (const uint32_t*)nullptr, st);
 #endif
     };
     auto timeit = [&](const unsigned char* W, const unsigned char* in, int n) {
@@ -314,12 +319,12 @@ int main(int argc, char** argv) {
             }
             const double span = (double)(tmax - tmin);
             const double mfma_cycles_per_wave = 48.0 * 72 * 32;   // issue time of a wave's matrix instructions on its SIMD (2 waves share it)
-            printf("{\"experiment\": \"stamps\", \"positions\": %d, \"launch_ms_event\": %.4f, \"waves_stamped\": %zu, \"cus_seen\": %zu, \"workgroups_per_cu_min_max\": [%zu, %zu], "
+            printf("{\"experiment\": \"stamps\", \"skip_path\": %s, \"positions\": %d, \"launch_ms_event\": %.4f, \"waves_stamped\": %zu, \"cus_seen\": %zu, \"workgroups_per_cu_min_max\": [%zu, %zu], "
                    "\"kernel_span_shader_cycles\": %.0f, \"shader_clock_ghz_from_event_time\": %.3f, \"realtime_ticks_span_100mhz\": %llu, "
                    "\"per_wave_mean_cycles\": {\"start_until_stage0_landed\": %.0f, \"k_loop\": %.0f, \"of_which_inside_barriers\": %.0f, \"epilogue_until_last_store_issued\": %.0f, "
                    "\"store_drain\": %.0f, \"total\": %.0f}, \"mfma_issue_cycles_per_simd_per_workgroup\": %.0f, \"k_loop_over_mfma_issue\": %.3f, "
                    "\"mean_gap_between_workgroups_on_a_cu_cycles\": %.0f, \"cu_busy_fraction_of_span\": %.3f}\n",
-                   n, ms, waves, per_cu.size(), min_wg, max_wg, span, span / (ms * 1e-3) / 1e9, rmax - rmin, sum_pro / waves, sum_loop / waves, sum_bar / waves,
+                   with_skip ? "true" : "false", n, ms, waves, per_cu.size(), min_wg, max_wg, span, span / (ms * 1e-3) / 1e9, rmax - rmin, sum_pro / waves, sum_loop / waves, sum_bar / waves,
                    sum_epi / waves, sum_drain / waves, sum_total / waves, 2 * mfma_cycles_per_wave, (sum_loop / waves) / (2 * mfma_cycles_per_wave),
                    gaps ? gap_sum / gaps : 0.0, busy_sum / (per_cu.size() * span));
             fflush(stdout);
