@@ -538,6 +538,53 @@ int raz_format_float_repr(double x, char* out32);
  * applied), 13 policy f32[64], 14 value f32 - what the net answered.  NULL for any other number. */
 void* raz_engine_device_ptr(raz_engine* e, int which);
 
+/* ---- raznet-train-v1: one training step of the net on the device (worker/optimize.py:73-86) ---------------
+ * The trainer holds the UNFOLDED graph of agent/model.py:28-72 in caller-owned device memory: parameters, Keras SGD momentum
+ * buffers, BatchNorm moving statistics, the saved tensors of one batch of at most max_batch rows and the partial sums of the
+ * ordered reductions.  Exact f32; the three 3x3 products of every trunk layer run on v_mfma_f32_16x16x4_f32.  No floating-point
+ * atomics: the same state and batches give the same bytes.  One device, one stream at a time, not re-entrant.
+ * Shapes: filters % 16 == 0 within 16..1024, cnn_filter_size 3, value_fc 1..16192, max_batch 1..65536; anything else:
+ * raz_trainer_bytes / raz_trainer_state_bytes 0, raz_trainer_create RAZ_EINVAL.
+ * THE TRAIN BLOB (raz_trainer_set_state / _get_state; f32, raz_trainer_state_bytes): parameters | moving statistics | momentum.
+ *   parameters: for every Conv2D + BatchNormalization pair in creation order (stem, the 2 R trunk layers, policy conv, value conv)
+ *     kernel [out][in][kh][kw], bias [out], gamma [out], beta [out]; then policy_out kernel [128][64] (in, out), bias [64];
+ *     dense_1 kernel [64][V], bias [V]; value_out kernel [V], bias [1];
+ *   moving statistics: per pair moving_mean [out], moving_variance [out];   momentum: as the parameters.
+ * The data set stays packed on the device (8 + 8 + 256 + 1 bytes per row): d_own / d_enemy u64[N], d_policy f32[N][64], d_z i8[N];
+ * d_idx u32[batch] names the rows of the batch.  AN INDEX >= N IS THE CALLER'S CONTRACT: it is not checked and reads out of bounds.
+ * raz_trainer_step: forward in training mode (batch statistics; moving statistics updated with momentum 0.99), the gradients of
+ *   mean_b sum_a -pi log(p + 1e-7) + mean_b (v - z)^2 + l2 sum w^2 over the Conv2D / Dense kernels (gradient term 2 l2 w), then
+ *   m <- 0.9 m - lr g, w <- w + m.  d_losses f32[2] receives the policy and the value loss of the batch (before the update).
+ * raz_trainer_backward: the same without the update of parameters, momentum and moving statistics; the gradients stay in the trainer.
+ * raz_trainer_read (device to device, ordered on `stream`; `bytes` must be the tensor's size) of the LAST step / backward:
+ *   RAZ_TRAIN_READ_GRADS   f32, the parameters' order and size (conv biases ahead of BatchNorm are exactly 0)
+ *   RAZ_TRAIN_READ_ACT     the post-ReLU output [batch][out][64] of pair `layer` (0 stem .. 2 R trunk, 2 R + 1 policy, 2 R + 2 value)
+ *   RAZ_TRAIN_READ_MEAN / _VAR   batch mean / biased batch variance [out] of pair `layer`
+ *   RAZ_TRAIN_READ_HIDDEN  dense_1's post-ReLU output [batch][V];  _POLICY the softmax [batch][64];  _VALUE the tanh [batch]
+ * RAZ_EINVAL and NO launch, state untouched: a NULL trainer or array, d_own / d_enemy not 8-byte or d_policy / d_idx / d_losses not
+ * 4-byte aligned, batch == 0 or > max_batch, a workspace that is NULL, not 256-byte aligned or below raz_trainer_bytes, a state
+ * or read size that does not match. */
+typedef struct raz_trainer raz_trainer;
+#define RAZ_TRAIN_READ_GRADS 0
+#define RAZ_TRAIN_READ_ACT 1
+#define RAZ_TRAIN_READ_MEAN 2
+#define RAZ_TRAIN_READ_VAR 3
+#define RAZ_TRAIN_READ_HIDDEN 4
+#define RAZ_TRAIN_READ_POLICY 5
+#define RAZ_TRAIN_READ_VALUE 6
+size_t raz_trainer_bytes(int filters, int res_layers, int value_fc, size_t max_batch);
+size_t raz_trainer_state_bytes(int filters, int res_layers, int value_fc);
+int raz_trainer_create(int filters, int res_layers, int value_fc, size_t max_batch, void* d_workspace, size_t workspace_bytes,
+                       raz_trainer** out, raz_stream_t stream);
+void raz_trainer_destroy(raz_trainer* t);
+int raz_trainer_set_state(raz_trainer* t, const float* d_blob, size_t bytes, raz_stream_t stream);
+int raz_trainer_get_state(raz_trainer* t, float* d_blob, size_t bytes, raz_stream_t stream);
+int raz_trainer_step(raz_trainer* t, const uint64_t* d_own, const uint64_t* d_enemy, const float* d_policy, const int8_t* d_z,
+                     const uint32_t* d_idx, size_t batch, float lr, float l2, float* d_losses, raz_stream_t stream);
+int raz_trainer_backward(raz_trainer* t, const uint64_t* d_own, const uint64_t* d_enemy, const float* d_policy, const int8_t* d_z,
+                         const uint32_t* d_idx, size_t batch, float l2, float* d_losses, raz_stream_t stream);
+int raz_trainer_read(raz_trainer* t, int which, int layer, void* d_out, size_t bytes, raz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

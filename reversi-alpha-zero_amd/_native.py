@@ -138,6 +138,17 @@ SIGNATURES.update({
     "raz_solve_batch_workspace_bytes": (c_size_t, [c_size_t, c_int]),
     "raz_solve_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                         c_uint32, c_void_p]),
+    # raznet-train-v1 (csrc/raz_train.hip); the trainer handle travels as c_void_p
+    "raz_trainer_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t]),
+    "raz_trainer_state_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "raz_trainer_create": (c_int, [c_int, c_int, c_int, c_size_t, c_void_p, c_size_t, POINTER(c_void_p), c_void_p]),
+    "raz_trainer_destroy": (None, [c_void_p]),
+    "raz_trainer_set_state": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "raz_trainer_get_state": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "raz_trainer_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p,
+                                 c_void_p]),
+    "raz_trainer_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_void_p]),
+    "raz_trainer_read": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -140,6 +140,68 @@ class ReversiNet(nn.Module):
         hdr = struct.pack("<8i", RAZNET_MAGIC, 1, self.filters, self.res_layers, self.value_fc, 3, 0, 0)
         return hdr + flat.tobytes()
 
+    # ---- train blob (raznet-train-v1, include/raz.h) ----------------------------------------------
+    def conv_bns(self):
+        """The Conv2D + BatchNormalization pairs in creation order: stem, trunk, policy conv, value conv."""
+        return [self.stem] + [c for blk in self.res for c in blk] + [self.policy_conv, self.value_conv]
+
+    def train_tensors(self):
+        """[(name, tensor)] of the train blob's PARAMETER section, in its order.  Dense kernels are listed as stored by torch
+        (out, in); the blob holds them (in, out)."""
+        out = []
+        for i, cb in enumerate(self.conv_bns()):
+            out += [(f"conv{i}.kernel", cb.conv.weight), (f"conv{i}.bias", cb.conv.bias),
+                    (f"bn{i}.gamma", cb.bn.weight), (f"bn{i}.beta", cb.bn.bias)]
+        for name, lin in (("policy_out", self.policy_fc), ("dense_1", self.value_fc1), ("value_out", self.value_fc2)):
+            out += [(f"{name}.kernel", lin.weight), (f"{name}.bias", lin.bias)]
+        return out
+
+    def stat_tensors(self):
+        out = []
+        for i, cb in enumerate(self.conv_bns()):
+            out += [(f"bn{i}.moving_mean", cb.bn.running_mean), (f"bn{i}.moving_variance", cb.bn.running_var)]
+        return out
+
+    @staticmethod
+    def _blob_form(name, t):
+        return t.detach().t() if name.endswith(".kernel") and t.dim() == 2 else t.detach()
+
+    def to_train_blob(self, momentum=None) -> np.ndarray:
+        """float32 array: parameters | moving statistics | momentum (zeros, or `momentum`: tensors in train_tensors() order and
+        torch shapes).  The unfolded graph, what raz_trainer_set_state takes."""
+        if self.filter_size != 3:
+            raise ValueError("raznet-train-v1 supports cnn_filter_size=3 only (all shipped configs)")
+        named = self.train_tensors()
+        params = [self._blob_form(n, t).reshape(-1) for n, t in named]
+        stats = [t.detach().reshape(-1) for _, t in self.stat_tensors()]
+        if momentum is None:
+            mom = [torch.zeros_like(p) for p in params]
+        else:
+            mom = [self._blob_form(n, m).reshape(-1) for (n, _), m in zip(named, momentum)]
+        return torch.cat([x.float().cpu().reshape(-1) for x in params + stats + mom]).numpy().astype(np.float32)
+
+    def load_train_blob(self, blob):
+        """Inverse of to_train_blob: fills parameters and moving statistics, returns the momentum tensors (torch shapes)."""
+        flat = torch.from_numpy(np.ascontiguousarray(np.asarray(blob, dtype=np.float32).reshape(-1)))
+        named, stats = self.train_tensors(), self.stat_tensors()
+        n_p, n_s = sum(t.numel() for _, t in named), sum(t.numel() for _, t in stats)
+        if flat.numel() != 2 * n_p + n_s:
+            raise ValueError(f"train blob of {flat.numel()} floats does not fit this net ({2 * n_p + n_s})")
+
+        def take(name, t, o):
+            v = flat[o:o + t.numel()]
+            v = v.view(t.shape[1], t.shape[0]).t() if name.endswith(".kernel") and t.dim() == 2 else v.view(t.shape)
+            return v.to(t.dtype), o + t.numel()
+        o, mom = 0, []
+        with torch.no_grad():
+            for name, t in named + stats:
+                v, o = take(name, t, o)
+                t.copy_(v)
+            for name, t in named:
+                v, o = take(name, t, o)
+                mom.append(v.clone().contiguous())
+        return mom
+
 
 def blob_float_count(F, R, V):
     return (F * 18 + F) + R * 2 * (F * F * 9 + F) + (2 * F + 2) + (128 * 64 + 64) + (F + 1) + (64 * V + V) + (V + 1)

@@ -1,6 +1,6 @@
 """Hyper-parameter tree with the reference's names and default values (reversi_zero/config.py:15-193)
-for the sections the self-play path reads: play, play_data, model, resource (+ opts).  The trainer /
-eval / GUI sections of the reference are outside the hot path and are not restated.
+for the sections the workers read: play, play_data, model, trainer, eval, resource (+ opts).  The GUI
+section of the reference is not restated.
 
 `load_config(yml_path)` overlays a reference YAML file (config/*.yml) the way
 manager.py:41-45 + moke_config.create_config do: recursive attribute assignment, unknown sections
@@ -48,6 +48,8 @@ class ResourceConfig(_Section):
         self.ggf_filename_tmpl = "self_play-%s.ggf"
         self.log_dir = os.path.join(self.project_dir, "logs")
         self.main_log_path = os.path.join(self.log_dir, "main.log")
+        self.tensorboard_log_dir = os.path.join(self.log_dir, "tensorboard")   # (TensorBoard logging itself is not restated)
+        self.force_learing_rate_file = os.path.join(self.data_dir, ".force-lr")   # (the reference's spelling)
         self.force_simulation_num_file = os.path.join(self.data_dir, ".force-sim")
         self.self_play_game_idx_file = os.path.join(self.data_dir, ".self-play-game-idx")
 
@@ -114,6 +116,20 @@ class EvaluateConfig(_Section):
         self.evaluate_latest_first = True
 
 
+class TrainerConfig(_Section):
+    def __init__(self):  # config.py:169-184
+        self.wait_after_save_model_ratio = 1
+        self.batch_size = 256
+        self.min_data_size_to_learn = 100000
+        self.epoch_to_checkpoint = 1
+        self.start_total_steps = 0
+        self.save_model_steps = 200
+        self.use_tensorboard = True   # read by nobody here: the worker logs through `logging`
+        self.logging_per_steps = 100
+        self.delete_self_play_after_number_of_training = 0
+        self.lr_schedules = [(0, 0.01), (150000, 0.001), (300000, 0.0001)]
+
+
 class ModelConfig(_Section):
     def __init__(self):  # config.py:187-193
         self.cnn_filter_num = 256
@@ -131,6 +147,7 @@ class Config(_Section):
         self.model = ModelConfig()
         self.play = PlayConfig()
         self.play_data = PlayDataConfig()
+        self.trainer = TrainerConfig()
         self.eval = EvaluateConfig()
 
 

@@ -1,10 +1,11 @@
 #!/bin/bash
 # Compiler-reported resources of the engine's kernels (VGPRs, spills, scratch, occupancy): hipcc -Rpass-analysis=kernel-resource-usage
-# over the engine's translation units, the batch solver's and the f16 trunk's, one line per kernel.  usage: tools/kernel_resources.sh [out.txt]
+# over the engine's translation units, the batch solver's, the f16 trunk's and the trainer's, one line per kernel.
+# usage: [RAZ_RESOURCE_FILES="a.hip b.hip"] tools/kernel_resources.sh [out.txt]
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-/dev/stdout}
 cd "$ROOT/reversi-alpha-zero_amd/csrc"
-for f in raz_engine.hip raz_engine_fused.hip raz_sweep.hip raz_solver_batch.hip raz_net_f16x3.hip; do
+for f in ${RAZ_RESOURCE_FILES:-raz_engine.hip raz_engine_fused.hip raz_sweep.hip raz_solver_batch.hip raz_net_f16x3.hip raz_train.hip}; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -c $f -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | \
   python3 -c "
 import re, sys
