@@ -9,10 +9,12 @@ import subprocess
 import numpy as np
 
 from conftest import ROOT, _locked
+from reversi_alpha_zero_amd.agent.trainer import DeviceTrainer
 
 EMU_DIR = os.path.join(ROOT, "tests", "native", "wave_emu")
 EMU_LIB = os.path.join(ROOT, "tests", "native", "libraz_emu.so")
 EMU_FULL_LIB = os.path.join(ROOT, "tests", "native", "libraz_emu_full.so")
+EMU_TRAIN_LIB = os.path.join(ROOT, "tests", "native", "libraz_emu_train.so")
 _libs = {}
 
 
@@ -39,6 +41,29 @@ def load(full=False):
                 fn.restype, fn.argtypes = res, args
         _libs[full] = lib
     return _libs[full]
+
+
+def load_train():
+    """The training kernels (csrc/raz_train.hip + raz_capi.hip, unchanged) on the emulator: libraz_emu_train.so, seconds to build."""
+    if "train" not in _libs:
+        with _locked("emu_train"):
+            r = subprocess.run(["make", "-C", EMU_DIR, "../libraz_emu_train.so"], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("wave-emulator build of the training kernels failed:\n" + r.stdout[-3000:] + r.stderr[-3000:])
+        from reversi_alpha_zero_amd import _native as N
+        lib = ctypes.CDLL(EMU_TRAIN_LIB)
+        for name, (res, args) in N.SIGNATURES.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
+        _libs["train"] = lib
+    return _libs["train"]
+
+
+def aligned(nbytes, align=256):
+    """(the array that owns the memory, an address in it aligned to `align` with nbytes behind it)"""
+    a = np.zeros(nbytes + align, dtype=np.uint8)
+    return a, (a.ctypes.data + align - 1) // align * align
 
 
 def _check(lib, rc, what):
@@ -222,3 +247,73 @@ class EmuEngine:
     def records(self, save_policy_of_tau_1=True, change_tau_turn=None):
         from reversi_alpha_zero_amd.engine import SelfPlayEngine
         return SelfPlayEngine.records(self, save_policy_of_tau_1, change_tau_turn)
+
+
+class EmuTrainer(DeviceTrainer):
+    """agent/trainer.py's DeviceTrainer on the emulated training kernels: the same nine raz_trainer_* entries on numpy host arrays,
+    stream NULL (the emulator runs every launch and copy to its end before it returns).  What DeviceTrainer derives from its reads
+    (activations, batch_stats, outputs, gradients, state, from_net / to_net) is inherited, so both hand the tests the same things."""
+
+    def __init__(self, net, max_batch, l2=1e-4):
+        import torch
+        from reversi_alpha_zero_amd.agent.model import ReversiNet
+        from reversi_alpha_zero_amd.agent.trainer import check_trainable
+        check_trainable(net)
+        self.lib = lib = load_train()
+        self.device, self.l2, self.max_batch = torch.device("cpu"), float(l2), int(max_batch)
+        self.F, self.R, self.V = net.filters, net.res_layers, net.value_fc
+        self.handle = ctypes.c_void_p()
+        nbytes = lib.raz_trainer_bytes(self.F, self.R, self.V, self.max_batch)
+        if not nbytes:
+            raise ValueError(f"raz_trainer_bytes refuses {self.F}x{self.R}x{self.V}, max_batch {self.max_batch}")
+        self.state_floats = lib.raz_trainer_state_bytes(self.F, self.R, self.V) // 4
+        self.workspace, base = aligned(nbytes)
+        _check(lib, lib.raz_trainer_create(self.F, self.R, self.V, self.max_batch, base, nbytes, ctypes.byref(self.handle), None),
+               "raz_trainer_create")
+        self.losses = np.zeros(2, dtype=np.float32)
+        self._shape_net = ReversiNet(self.F, self.R, self.V)
+        self.last_batch = 0
+        self.from_net(net)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.raz_trainer_destroy(self.handle)
+            self.handle = None
+
+    def set_blob(self, blob):
+        b = np.ascontiguousarray(blob, dtype=np.float32)
+        _check(self.lib, self.lib.raz_trainer_set_state(self.handle, b.ctypes.data, b.nbytes, None), "raz_trainer_set_state")
+
+    def get_blob(self):
+        b = np.empty(self.state_floats, dtype=np.float32)
+        _check(self.lib, self.lib.raz_trainer_get_state(self.handle, b.ctypes.data, b.nbytes, None), "raz_trainer_get_state")
+        return b
+
+    @staticmethod
+    def _args(own, enemy, policy, z, idx):
+        own, enemy = np.ascontiguousarray(own, dtype=np.uint64), np.ascontiguousarray(enemy, dtype=np.uint64)
+        policy, z = np.ascontiguousarray(policy, dtype=np.float32), np.ascontiguousarray(z, dtype=np.int8)
+        idx = np.ascontiguousarray(idx).astype(np.uint32)
+        if not (own.size == enemy.size == z.size and policy.size == 64 * own.size):
+            raise ValueError("own, enemy, policy [N,64] and z must describe the same N rows")
+        return own, enemy, policy, z, idx
+
+    def backward(self, own, enemy, policy, z, idx):
+        a = self._args(own, enemy, policy, z, idx)
+        _check(self.lib, self.lib.raz_trainer_backward(self.handle, *(x.ctypes.data for x in a), a[4].size, self.l2,
+                                                       self.losses.ctypes.data, None), "raz_trainer_backward")
+        self.last_batch = a[4].size
+        return tuple(float(x) for x in self.losses)
+
+    def step(self, own, enemy, policy, z, idx, lr, sync=True):
+        a = self._args(own, enemy, policy, z, idx)
+        _check(self.lib, self.lib.raz_trainer_step(self.handle, *(x.ctypes.data for x in a), a[4].size, float(lr), self.l2,
+                                                   self.losses.ctypes.data, None), "raz_trainer_step")
+        self.last_batch = a[4].size
+        return tuple(float(x) for x in self.losses)
+
+    def read(self, which, layer, shape):
+        import torch
+        out = np.empty(shape, dtype=np.float32)
+        _check(self.lib, self.lib.raz_trainer_read(self.handle, which, layer, out.ctypes.data, out.nbytes, None), "raz_trainer_read")
+        return torch.from_numpy(out)
