@@ -584,6 +584,18 @@ int raz_trainer_step(raz_trainer* t, const uint64_t* d_own, const uint64_t* d_en
 int raz_trainer_backward(raz_trainer* t, const uint64_t* d_own, const uint64_t* d_enemy, const float* d_policy, const int8_t* d_z,
                          const uint32_t* d_idx, size_t batch, float l2, float* d_losses, raz_stream_t stream);
 int raz_trainer_read(raz_trainer* t, int which, int layer, void* d_out, size_t bytes, raz_stream_t stream);
+/* raznet-train-v2, opt-in: the same step, train blob and fixed summation orders with the three 3x3 products
+ * of every trunk layer on the f16 matrix cores - every f32 operand as two halfs under a per-tensor power-of-two scale, three
+ * v_mfma_f32_32x32x16_f16 per product into one f32 accumulator, un-scaled once.  precision RAZ_TRAIN_F32: raz_trainer_bytes /
+ * raz_trainer_create to the byte; RAZ_TRAIN_F16X3: v2 (a larger workspace; reproducible, but not v1's bytes); any other value:
+ * raz_trainer_bytes2 returns 0 and raz_trainer_create2 RAZ_EINVAL, both with a message.  raz_trainer_precision: what a trainer was
+ * created with (RAZ_EINVAL for NULL).  Every other entry takes either kind of trainer. */
+#define RAZ_TRAIN_F32 0
+#define RAZ_TRAIN_F16X3 1
+size_t raz_trainer_bytes2(int filters, int res_layers, int value_fc, size_t max_batch, int precision);
+int raz_trainer_create2(int filters, int res_layers, int value_fc, size_t max_batch, int precision, void* d_workspace,
+                        size_t workspace_bytes, raz_trainer** out, raz_stream_t stream);
+int raz_trainer_precision(const raz_trainer* t);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,10 @@ SIGNATURES.update({
                                  c_void_p]),
     "raz_trainer_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_void_p]),
     "raz_trainer_read": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    # raznet-train-v2: the same with a precision (0 f32, 1 split f16)
+    "raz_trainer_bytes2": (c_size_t, [c_int, c_int, c_int, c_size_t, c_int]),
+    "raz_trainer_create2": (c_int, [c_int, c_int, c_int, c_size_t, c_int, c_void_p, c_size_t, POINTER(c_void_p), c_void_p]),
+    "raz_trainer_precision": (c_int, [c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

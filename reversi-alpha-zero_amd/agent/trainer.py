@@ -174,26 +174,39 @@ class TorchTrainer:
         return [a.cpu() for a in self.acts]
 
 
+PRECISIONS = {"f32": 0, "f16x3": 1}   # include/raz.h RAZ_TRAIN_F32 (raznet-train-v1), RAZ_TRAIN_F16X3 (raznet-train-v2)
+
+
+def precision_code(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision={precision!r}: 'f32' (raznet-train-v1) or 'f16x3' (raznet-train-v2)")
+    return PRECISIONS[precision]
+
+
 class DeviceTrainer:
     """The HIP trainer.  All arrays given to step / backward are moved to the trainer's device if they are not there already;
-    keep the data set resident (torch tensors on the device) to launch kernels only."""
+    keep the data set resident (torch tensors on the device) to launch kernels only.  precision="f32" is raznet-train-v1;
+    "f16x3" is raznet-train-v2: the trunk's 3x3 products on the f16 matrix cores over split operands -
+    as reproducible as v1, not v1's bytes."""
 
     READ_GRADS, READ_ACT, READ_MEAN, READ_VAR, READ_HIDDEN, READ_POLICY, READ_VALUE = range(7)
 
-    def __init__(self, net, max_batch, device="cuda:0", l2=1e-4):
+    def __init__(self, net, max_batch, device="cuda:0", l2=1e-4, precision="f32"):
+        code = precision_code(precision)
         from .. import _native as N
         check_trainable(net)
+        self.precision = precision
         self.N, self.device, self.l2, self.max_batch = N, torch.device(device), float(l2), int(max_batch)
         self.F, self.R, self.V = net.filters, net.res_layers, net.value_fc
         self.handle = ctypes.c_void_p()
-        nbytes = N.lib.raz_trainer_bytes(self.F, self.R, self.V, self.max_batch)
+        nbytes = N.lib.raz_trainer_bytes2(self.F, self.R, self.V, self.max_batch, code)   # (precision 0: raz_trainer_bytes / _create to the byte)
         if not nbytes:
-            raise ValueError(f"raz_trainer_bytes refuses {self.F}x{self.R}x{self.V}, max_batch {self.max_batch}")
+            raise ValueError(f"raz_trainer_bytes2 refuses {self.F}x{self.R}x{self.V}, max_batch {self.max_batch}, precision {precision!r}")
         self.state_floats = N.lib.raz_trainer_state_bytes(self.F, self.R, self.V) // 4
         with torch.cuda.device(self.device):
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            N.check(N.lib.raz_trainer_create(self.F, self.R, self.V, self.max_batch, self.workspace.data_ptr(), nbytes,
-                                             ctypes.byref(self.handle), N.current_stream_ptr()), "raz_trainer_create")
+            N.check(N.lib.raz_trainer_create2(self.F, self.R, self.V, self.max_batch, code, self.workspace.data_ptr(), nbytes,
+                                              ctypes.byref(self.handle), N.current_stream_ptr()), "raz_trainer_create2")
         self.losses = torch.zeros(2, dtype=torch.float32, device=self.device)
         self._shape_net = ReversiNet(self.F, self.R, self.V)
         self.last_batch = 0

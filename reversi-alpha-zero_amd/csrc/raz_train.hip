@@ -14,7 +14,11 @@
 // element for the dense layers.  No floating-point atomics anywhere: every sum over the batch has one fixed order, so two
 // trainers given the same state and batches hold the same bytes.  Per-channel and per-weight sums over the batch outside the
 // matrix products accumulate in f64 and round once.
+//
+// raznet-train-v2 (precision RAZ_TRAIN_F16X3, opt-in through raz_trainer_create2) is the same step with the three trunk products on
+// the f16 matrix cores over split operands: raz_train_f16x3.h.  Precision RAZ_TRAIN_F32 launches exactly what it always did.
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 #include <new>
 #include <vector>
 #include "raz_bitboard.h"
@@ -452,6 +456,8 @@ __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ w, float* __res
     w[e] = w[e] + mv;
 }
 
+#include "raz_train_f16x3.h"
+
 inline size_t up64(size_t floats) { return (floats + 63) & ~(size_t)63; }   // 256-byte granules
 
 }  // namespace
@@ -471,6 +477,10 @@ struct raz_trainer {
     float *P, *ST, *M, *G;
     float *pol, *h1, *vpre, *val, *dlogit, *dh1, *dvpre, *dph, *dvh, *dyp, *dyv, *lp, *lv;
     float *gb, *db, *eb, *partial;
+    int precision;           // RAZ_TRAIN_F32 (v1) or RAZ_TRAIN_F16X3 (v2); the rest: v2 alone
+    unsigned char* wimg;     // one split weight image (raz_train_f16x3.h), rebuilt ahead of every product that reads one
+    float* sc;               // per pair 8 floats: (S, 1 / S) of its kernel, of its input activations, of its output gradient
+    unsigned* amax;          // partial maxima of k_absmax_part
 };
 
 namespace {
@@ -526,6 +536,11 @@ size_t layout(raz_trainer* t, float* base) {
     t->gb = take(mb * F * 64); t->db = take(mb * F * 64); t->eb = take(mb * F * 64);
     const size_t S = mb < (size_t)MAX_SPLIT ? mb : (size_t)MAX_SPLIT;
     t->partial = take(S * F * F * 9);
+    if (t->precision == RAZ_TRAIN_F16X3) {   // appended: precision 0 keeps its layout to the byte
+        t->wimg = (unsigned char*)take((size_t)((F + X3_OCT - 1) / X3_OCT) * (F / 16) * (X3_WCHUNK / 4));
+        t->sc = take((size_t)NL * 8);
+        t->amax = (unsigned*)take(X3_MAX_PARTS);
+    }
     return o;
 }
 
@@ -544,6 +559,25 @@ void bn_bwd(raz_trainer* t, int i, float* g, float* dy, int keep, int B, hipStre
                        (const float*)l.binv, (const float*)(t->P + l.g), t->G + l.g, t->G + l.be, dy, keep, B, l.cout);
 }
 
+// ---- raznet-train-v2: the scale of a tensor, and the three products of trunk pair i ------------------------------------------------
+void x3_scale(raz_trainer* t, const float* x, size_t n, float* sc, hipStream_t s) {
+    const size_t want = (n + 1023) / 1024;
+    const unsigned parts = (unsigned)(want < (size_t)X3_MAX_PARTS ? want : (size_t)X3_MAX_PARTS);
+    hipLaunchKernelGGL(k_absmax_part, dim3(parts), dim3(256), 0, s, x, n, t->amax);
+    hipLaunchKernelGGL(k_scale_f16x3, dim3(1), dim3(256), 0, s, (const unsigned*)t->amax, (int)parts, sc);
+}
+
+// transposed: the input-gradient form.  scin: the scale of `in`.
+void x3_conv(raz_trainer* t, int i, bool transposed, const float* in, const float* scin, const float* bias, float* out, const float* add,
+             int B, hipStream_t s) {
+    const int F = t->F, ntile = (F + X3_OCT - 1) / X3_OCT;
+    const float* scw = t->sc + (size_t)i * 8;
+    hipLaunchKernelGGL(k_wimage_f16x3, dim3(blocks((size_t)ntile * (F / 16) * 9 * 128)), dim3(256), 0, s, (const float*)(t->P + t->L[i].w), scw,
+                       t->wimg, F, transposed ? 1 : 0);
+    hipLaunchKernelGGL(k_tconv_f16x3, dim3((unsigned)((B + 3) / 4), (unsigned)ntile), dim3(256), 0, s, (const unsigned char*)t->wimg, scw, scin,
+                       bias, in, out, add, B, F, F);
+}
+
 void forward(raz_trainer* t, const uint64_t* own, const uint64_t* enemy, const float* policy, const int8_t* z, const uint32_t* idx,
              int B, bool update, float* d_losses, hipStream_t s) {
     const int F = t->F, R = t->R, V = t->V, T = 2 * R, IP = 2 * R + 1, IV = 2 * R + 2;
@@ -554,6 +588,12 @@ void forward(raz_trainer* t, const uint64_t* own, const uint64_t* enemy, const f
     bn_fwd(t, 0, nullptr, B, update, s);
     const dim3 grid((unsigned)((B + 3) / 4), (unsigned)(F / 16));
     for (int i = 1; i <= T; ++i) {
+        if (t->precision == RAZ_TRAIN_F16X3) {
+            float* sc = t->sc + (size_t)i * 8;
+            x3_scale(t, P + L[i].w, (size_t)F * F * 9, sc, s);
+            x3_scale(t, L[i - 1].a, (size_t)B * F * 64, sc + 2, s);
+            x3_conv(t, i, false, L[i - 1].a, sc + 2, P + L[i].b, L[i].y, nullptr, B, s);
+        } else
         hipLaunchKernelGGL(k_tconv<false>, grid, dim3(256), 0, s, (const float*)(P + L[i].w), (const float*)(P + L[i].b),
                            (const float*)L[i - 1].a, L[i].y, (const float*)nullptr, B, F, F);
         bn_fwd(t, i, (i & 1) ? nullptr : L[i - 2].a, B, update, s);
@@ -575,6 +615,12 @@ void forward(raz_trainer* t, const uint64_t* own, const uint64_t* enemy, const f
 
 void conv_wgrad(raz_trainer* t, int i, const float* dy, const float* x, int B, float l2, hipStream_t s) {
     const int F = t->F, S = B < MAX_SPLIT ? B : MAX_SPLIT;
+    if (t->precision == RAZ_TRAIN_F16X3) {   // dy's scale first: the input gradient of the same pair reads it too
+        float* sc = t->sc + (size_t)i * 8;
+        x3_scale(t, dy, (size_t)B * F * 64, sc + 4, s);
+        hipLaunchKernelGGL(k_twgrad_f16x3, dim3((unsigned)((F + 63) / 64), (unsigned)((F + 31) / 32), (unsigned)S), dim3(256), 0, s, dy, x,
+                           (const float*)(sc + 4), (const float*)(sc + 2), t->partial, B, F, F);
+    } else
     hipLaunchKernelGGL(k_twgrad, dim3((unsigned)((F + 63) / 64), (unsigned)(F / 16), (unsigned)S), dim3(256), 0, s, dy, x, t->partial, B, F, F);
     const size_t n = (size_t)F * F * 9;
     hipLaunchKernelGGL(k_twgrad_fold, dim3(blocks(n)), dim3(256), 0, s, (const float*)t->partial, (const float*)(t->P + t->L[i].w),
@@ -612,10 +658,14 @@ int backward(raz_trainer* t, const uint64_t* own, const uint64_t* enemy, const u
         const int l1 = 1 + 2 * r, l2i = 2 + 2 * r;
         bn_bwd(t, l2i, t->gb, t->db, 1, B, s);   // gb keeps the masked gradient: the skip path's share
         conv_wgrad(t, l2i, t->db, L[l1].a, B, l2, s);
+        if (t->precision == RAZ_TRAIN_F16X3) x3_conv(t, l2i, true, t->db, t->sc + (size_t)l2i * 8 + 4, nullptr, t->eb, nullptr, B, s);
+        else
         hipLaunchKernelGGL(k_tconv<true>, grid, dim3(256), 0, s, (const float*)(P + L[l2i].w), (const float*)nullptr, (const float*)t->db,
                            t->eb, (const float*)nullptr, B, F, F);
         bn_bwd(t, l1, t->eb, t->db, 0, B, s);
         conv_wgrad(t, l1, t->db, L[l1 - 1].a, B, l2, s);
+        if (t->precision == RAZ_TRAIN_F16X3) x3_conv(t, l1, true, t->db, t->sc + (size_t)l1 * 8 + 4, nullptr, t->gb, t->gb, B, s);
+        else
         hipLaunchKernelGGL(k_tconv<true>, grid, dim3(256), 0, s, (const float*)(P + L[l1].w), (const float*)nullptr, (const float*)t->db,
                            t->gb, (const float*)t->gb, B, F, F);
     }
@@ -639,43 +689,80 @@ int check_batch(raz_trainer* t, const void* own, const void* enemy, const void* 
 
 extern "C" {
 
-size_t raz_trainer_bytes(int filters, int res_layers, int value_fc, size_t max_batch) {
+size_t raz_trainer_bytes2(int filters, int res_layers, int value_fc, size_t max_batch, int precision) {
+    if (precision != RAZ_TRAIN_F32 && precision != RAZ_TRAIN_F16X3) {
+        raz_fail(RAZ_EINVAL, "raz_trainer_bytes2: precision is RAZ_TRAIN_F32 (0) or RAZ_TRAIN_F16X3 (1)");
+        return 0;
+    }
     if (max_batch > 65536 || !shape_ok(filters, res_layers, value_fc, (int)max_batch)) return 0;
     raz_trainer t;
-    t.F = filters; t.R = res_layers; t.V = value_fc; t.max_batch = (int)max_batch;
+    t.F = filters; t.R = res_layers; t.V = value_fc; t.max_batch = (int)max_batch; t.precision = precision;
     return layout(&t, nullptr) * sizeof(float);
+}
+
+size_t raz_trainer_bytes(int filters, int res_layers, int value_fc, size_t max_batch) {
+    return raz_trainer_bytes2(filters, res_layers, value_fc, max_batch, RAZ_TRAIN_F32);
 }
 
 size_t raz_trainer_state_bytes(int filters, int res_layers, int value_fc) {
     if (!shape_ok(filters, res_layers, value_fc, 1)) return 0;
     raz_trainer t;
-    t.F = filters; t.R = res_layers; t.V = value_fc; t.max_batch = 1;
+    t.F = filters; t.R = res_layers; t.V = value_fc; t.max_batch = 1; t.precision = RAZ_TRAIN_F32;
     layout(&t, nullptr);
     return (2 * t.np + t.ns) * sizeof(float);
 }
 
-int raz_trainer_create(int filters, int res_layers, int value_fc, size_t max_batch, void* d_workspace, size_t workspace_bytes,
-                       raz_trainer** out, raz_stream_t stream) {
-    if (!out) return raz_fail(RAZ_EINVAL, "raz_trainer_create: NULL out");
+// Both create entries.  `who`: the entry called, `spec` / `sizer`: the specification and the size entry its messages name.
+static int trainer_create(const char* who, const char* spec, const char* sizer, int filters, int res_layers, int value_fc, size_t max_batch,
+                          int precision, void* d_workspace, size_t workspace_bytes, raz_trainer** out, raz_stream_t stream) {
+    char msg[256];
+    auto fail = [&](int code, const char* what) {
+        snprintf(msg, sizeof msg, "%s: %s", who, what);
+        return raz_fail(code, msg);
+    };
+    if (!out) return fail(RAZ_EINVAL, "NULL out");
     *out = nullptr;
-    if (max_batch > 65536 || !shape_ok(filters, res_layers, value_fc, (int)max_batch))
-        return raz_fail(RAZ_EINVAL, "raz_trainer_create: raznet-train-v1 takes filters % 16 == 0 (16..1024), cnn_filter_size 3, "
-                                    "value_fc 1..16192, max_batch 1..65536");
-    const size_t need = raz_trainer_bytes(filters, res_layers, value_fc, max_batch);
-    if (!d_workspace || ((uintptr_t)d_workspace & 255)) return raz_fail(RAZ_EINVAL, "raz_trainer_create: workspace NULL or not 256-byte aligned");
-    if (workspace_bytes < need) return raz_fail(RAZ_EINVAL, "raz_trainer_create: workspace too small (raz_trainer_bytes)");
+    if (precision != RAZ_TRAIN_F32 && precision != RAZ_TRAIN_F16X3)
+        return fail(RAZ_EINVAL, "precision is RAZ_TRAIN_F32 (0) or RAZ_TRAIN_F16X3 (1)");
+    if (max_batch > 65536 || !shape_ok(filters, res_layers, value_fc, (int)max_batch)) {
+        snprintf(msg, sizeof msg, "%s: %s takes filters %% 16 == 0 (16..1024), cnn_filter_size 3, value_fc 1..16192, max_batch 1..65536", who, spec);
+        return raz_fail(RAZ_EINVAL, msg);
+    }
+    const size_t need = raz_trainer_bytes2(filters, res_layers, value_fc, max_batch, precision);
+    if (!d_workspace || ((uintptr_t)d_workspace & 255)) return fail(RAZ_EINVAL, "workspace NULL or not 256-byte aligned");
+    if (workspace_bytes < need) {
+        snprintf(msg, sizeof msg, "%s: workspace too small (%s)", who, sizer);
+        return raz_fail(RAZ_EINVAL, msg);
+    }
     raz_trainer* t = new (std::nothrow) raz_trainer;
-    if (!t) return raz_fail(RAZ_ENOMEM, "raz_trainer_create: no host memory");
+    if (!t) return fail(RAZ_ENOMEM, "no host memory");
     t->F = filters; t->R = res_layers; t->V = value_fc; t->max_batch = (int)max_batch; t->last_batch = 0;
+    t->precision = precision; t->wimg = nullptr; t->sc = nullptr; t->amax = nullptr;
     layout(t, (float*)d_workspace);
     hipError_t e = hipMemsetAsync(d_workspace, 0, need, (hipStream_t)stream);
     if (e != hipSuccess) {
         delete t;
-        return raz_fail_hip(e, "raz_trainer_create: hipMemsetAsync");
+        snprintf(msg, sizeof msg, "%s: hipMemsetAsync", who);
+        return raz_fail_hip(e, msg);
     }
     *out = t;
     return RAZ_OK;
 }
+
+int raz_trainer_create2(int filters, int res_layers, int value_fc, size_t max_batch, int precision, void* d_workspace,
+                        size_t workspace_bytes, raz_trainer** out, raz_stream_t stream) {
+    return trainer_create("raz_trainer_create2", precision == RAZ_TRAIN_F16X3 ? "raznet-train-v2 (precision RAZ_TRAIN_F16X3)" : "raznet-train-v1",
+                          "raz_trainer_bytes2 at this precision", filters, res_layers, value_fc, max_batch, precision, d_workspace,
+                          workspace_bytes, out, stream);
+}
+
+int raz_trainer_create(int filters, int res_layers, int value_fc, size_t max_batch, void* d_workspace, size_t workspace_bytes,
+                       raz_trainer** out, raz_stream_t stream) {
+    return trainer_create("raz_trainer_create", "raznet-train-v1", "raz_trainer_bytes", filters, res_layers, value_fc, max_batch, RAZ_TRAIN_F32,
+                          d_workspace, workspace_bytes, out, stream);
+}
+
+int raz_trainer_precision(const raz_trainer* t) { return t ? t->precision : RAZ_EINVAL; }
 
 void raz_trainer_destroy(raz_trainer* t) { delete t; }
 

@@ -21,6 +21,8 @@ logger = getLogger(__name__)
 # Which step runs by default: measured on one MI355X at the 256x10 net and batch 256 (tools/bench_train.py, DESIGN.md section 4.8,
 # profiles/r7/train_step_timing.json) the HIP step takes 18.6 ms and fp32 torch-ROCm's 14.6 ms ON THE GPU, so the default is the torch
 # restatement, run on the GPU (default_device); backend="hip" is the faster step for the mini net (1.2 against 2.7 ms) and the bit-reproducible one everywhere.
+# backend="hip" with precision="f16x3" (raznet-train-v2, opt-in) took 11.4 ms in one process with v1's 18.7 and torch's 15.2 (profiles/r10/
+# train_step_timing_f16x3.json); whether a default should follow is decided from those numbers, not here.
 DEFAULT_BACKEND = "torch"
 
 
@@ -31,14 +33,21 @@ def default_device(backend):
     return "cuda:0" if backend == "hip" or torch.cuda.is_available() else "cpu"
 
 
-def start(config, backend=None, seed=0, max_epochs=None, device=None):
-    return OptimizeWorker(config, backend=backend or DEFAULT_BACKEND, seed=seed, device=device).start(max_epochs=max_epochs)
+def start(config, backend=None, seed=0, max_epochs=None, device=None, precision=None):
+    return OptimizeWorker(config, backend=backend or DEFAULT_BACKEND, seed=seed, device=device, precision=precision).start(max_epochs=max_epochs)
 
 
 class OptimizeWorker:
-    def __init__(self, config, backend=DEFAULT_BACKEND, seed=0, device=None):
+    def __init__(self, config, backend=DEFAULT_BACKEND, seed=0, device=None, precision=None):
+        """precision (backend="hip" alone): "f32" - raznet-train-v1, what None means - or "f16x3", raznet-train-v2."""
         if backend not in ("hip", "torch"):
             raise ValueError(f"backend={backend!r}: 'hip' or 'torch'")
+        if precision is not None:
+            if backend != "hip":
+                raise ValueError(f"precision={precision!r} is an option of backend='hip'; backend='torch' trains in fp32")
+            from ..agent.trainer import precision_code
+            precision_code(precision)
+        self.precision = precision or "f32"
         self.config = config
         self.backend, self.seed, self.device = backend, seed, device or default_device(backend)
         self.model = None  # type: ReversiModel
@@ -83,7 +92,7 @@ class OptimizeWorker:
         tc, l2 = self.config.trainer, self.config.model.l2_reg
         self.lr = 1e-2
         if self.backend == "hip":
-            self.trainer = DeviceTrainer(self.model.model, max_batch=tc.batch_size, device=self.device, l2=l2)
+            self.trainer = DeviceTrainer(self.model.model, max_batch=tc.batch_size, device=self.device, l2=l2, precision=self.precision)
         else:
             self.trainer = TorchTrainer(self.model.model, max_batch=tc.batch_size, device=self.device, l2=l2)
 
