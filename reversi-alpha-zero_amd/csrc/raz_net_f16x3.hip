@@ -19,16 +19,28 @@
 //
 // GEMM view per layer: D[oc, sq] += W[oc, k] * X[k, sq], k = (chunk, tap, channel in chunk).
 //   workgroup = 8 waves = 128 output channels x 8 positions (one workgroup per CU, 2 waves per SIMD, <= 256 VGPRs);
-//               wave = 128 oc x 64 squares of ONE position = 4 x 2 MFMA tiles (128 accumulator registers)
-//   K loop    = 16 chunks x 3 tap groups = 48 stages; a stage's weights (24 KB: 3 taps x 16 channels x 128 oc x {hi, lo})
-//               and, once per chunk, the 8 positions' activations (32 KB) arrive by LDS-DMA in a double buffer while the
+//               wave = 64 oc x 4 board rows of FOUR positions = 2 x 4 MFMA tiles (128 accumulator registers): wave w takes the oc
+//               half w & 1, the position group (w >> 1) & 1 (positions 0-3 or 4-7) and the row half w >> 2 (board rows 0-3 or 4-7);
+//               N tile j is board row 4 half + j, its column c is position c >> 3, file c & 7
+//   K loop    = 16 chunks x 3 tap groups (dy = -1, 0, +1) = 48 stages; a stage's weights (24 KB: 3 taps x 16 channels x 128 oc x
+//               {hi, lo}) and, once per chunk, the 8 positions' activations (32 KB) arrive by LDS-DMA in a double buffer while the
 //               previous stage's 3 taps x 8 tiles x 3 MFMAs per wave run: one barrier per stage, no register staging
-//   taps      = per-lane LDS addresses precomputed once (18 VGPRs): square + tap shift, or - off the board - a slot of a
-//               zero row in the same bank class, so there are no predicates and no halo in the image
-//   LDS reads = ds_read_b128, conflict-free by construction: lanes 0-31 read consecutive 16-byte slots (squares or channels),
-//               lanes 32-63 the other k-group's plane; 0.5 reads per MFMA
-//   epilogue  = the wave's halves trade accumulators so that a lane owns the 8 channels of one square; * 1/S, + bias, (+ skip),
-//               relu, split into (hi, lo), 16-byte stores: a wave writes whole 1 KiB planes
+//   row skip  = with a tile being ONE board row, the taps dy = -1 of row 0 and dy = +1 of row 7 are whole all-zero B operands: a
+//               top-half wave issues neither reads nor matrix instructions for its tile 0 in the stages dy = -1, a bottom-half wave
+//               none for its tile 3 in the stages dy = +1 (6 of 72 tile-taps: 198 instead of 216 matrix instructions per wave and
+//               chunk, v3 66 instead of 72).  A skipped instruction added exact zeros to an accumulator that started at +0, and the
+//               others keep their order per accumulator, so no bit moves.  Waves w and w + 4 share a SIMD (HW_ID in the stamps:
+//               profiles/r11), one of each row half, so every SIMD saves the same 6 tile-taps in 2 stages of 3
+//   taps      = three per-lane LDS addresses (dx = -1, 0, +1) at board row 4 half - 1; tile j under dy adds (j + dy + 1) * 128 as an
+//               immediate.  A file off the board reads a zero area instead, at the bank class of the slot it would have read (the
+//               area spans every immediate), so there are no predicates and no halo in the image; no row off the board is ever read
+//   LDS reads = ds_read_b128, conflict-free by construction: A - lanes 0-31 read consecutive 16-byte slots (channels), lanes 32-63
+//               the other k-group's plane; B - 8 files x 4 positions, the positions 4,096 + 128 bytes apart (act_pos_off);
+//               0.5 reads per MFMA
+//   epilogue  = the wave's halves trade accumulators (tiles 2 k and 2 k + 1) so that a lane owns the 8 channels of one (position,
+//               row, file); * 1/S, + bias, (+ skip), relu, split into (hi, lo), 16-byte stores in 128-byte runs (a row's 8 files).
+//               Whether a lane stores and raises its position's range flag is the lane's own position's liveness; a wave leaves
+//               early only when none of its four positions is live
 //
 // "raznet-forward-v3" (SPLIT = false below; opt-in, raz_net.reserved = 8) is v2 with every lo half taken as zero: activations and
 // weights are the hi halfs alone, out = f16(relu(acc / S + bias [+ skip])) with ONE matrix instruction per product.  Same tiling,
@@ -56,11 +68,17 @@ constexpr int OCT = 128;                         // output channels per workgrou
 constexpr int NWAVE = 8;                         // waves per workgroup = positions per workgroup
 constexpr int W_STAGE = 3 * 2 * 2 * OCT * 16;    // 24,576 B: [tap 3][k-group 2][hi/lo][oc 128][16 B]
 constexpr int ACT_POS = 4 * 64 * 16;             // 4,096 B: [plane 4][square 64][16 B]
-constexpr int ACT_IMG = NWAVE * ACT_POS + 1280;  // one chunk's image: 8 positions + two zero rows of 256 B, 1,024 B apart
+constexpr int Z_OFF = NWAVE * (ACT_POS + 128);   // the zero area inside an image, after the 8 positions (act_pos_off): 33,792
+constexpr int Z_BYTES = 2048;                    // a bank-class slot (< 256) + a row offset (<= 5 * 128) + the lo plane's 1,024 + 16 B
+constexpr int ACT_IMG = Z_OFF + Z_BYTES;         // one chunk's image: 8 positions + the zero area (35,840 B)
 constexpr int LDS_W = 0;                         // two weight stages (double buffer)
 constexpr int LDS_ACT = 2 * W_STAGE;             // two activation images (double buffer)
-constexpr int LDS_BYTES = LDS_ACT + 2 * ACT_IMG; // 117,248 B: one workgroup of 8 waves per CU
-constexpr int Z_OFF = NWAVE * ACT_POS;           // the zero rows inside an image (at Z_OFF and Z_OFF + 1024)
+constexpr int LDS_BYTES = LDS_ACT + 2 * ACT_IMG; // 120,832 B: one workgroup of 8 waves per CU
+// Where position p (0..7) of the workgroup starts inside an image.  A B read takes 8 files x 4 positions; the LDS serves a 16-byte
+// read in the lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (and the same + 32), i.e. files 0-3 of positions 0 and 3 with
+// files 4-7 of positions 1 and 2, and the reverse.  With every position on the same 256-byte bank row those would meet two by two;
+// with the positions 4,096 + 128 bytes apart (the odd ones half a bank row up), each group covers the 16 slots of a bank row once.
+constexpr int act_pos_off(int p) { return p * (ACT_POS + 128); }
 
 // Timeline instrumentation of the conv kernel, compiled in ONLY by tools/probe_conv.hip (which includes this file with
 // RAZ_F16X3_STAMPS defined): per wave 8 words - s_memtime at entry [0], when stage 0 has landed [1], at the end of the K loop [2],
@@ -126,6 +144,41 @@ __device__ __forceinline__ void halves_trade(float a, float b, int upper, float&
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),                     \
                                      (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
+// One stage (tap group TG = dy + 1: three taps dx = -1, 0, +1) of a wave's tile: 2 output-channel tiles x the board rows J0 .. J1 - 1
+// of its row half.  Row j under tap dy reads board row 4 half + j + dy, which lies (j + TG) * 128 bytes above the row the three
+// per-lane addresses `boff` point at (4 half - 1).  Per accumulator the instructions come in the order they always had: tap
+// 0 .. 8, each al*bh, ah*bl, ah*bh.
+template <bool SPLIT, int TG, int J0, int J1>
+__device__ __forceinline__ void conv_stage(const unsigned char* lds, uint32_t wbase, uint32_t abase, const uint32_t (&boff)[3],
+                                           f32x16 (&acc)[2][4]) {
+#pragma unroll
+    for (int tt = 0; tt < 3; ++tt) {
+        h8 bh[4], bl[4];
+#pragma unroll
+        for (int j = J0; j < J1; ++j) {
+            const uint32_t at = abase + boff[tt] + (j + TG) * 128;   // (summed in 32 bits: boff alone may lie below the image)
+            bh[j] = *(const h8*)(lds + at);
+            if constexpr (SPLIT) bl[j] = *(const h8*)(lds + at + 1024);
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const h8 ah = *(const h8*)(lds + wbase + tt * 8192 + m * 512);
+            if constexpr (SPLIT) {
+                const h8 al = *(const h8*)(lds + wbase + tt * 8192 + m * 512 + 2048);
+#pragma unroll
+                for (int j = J0; j < J1; ++j) {
+                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[m][j], 0, 0, 0);
+                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[j], acc[m][j], 0, 0, 0);
+                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[m][j], 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int j = J0; j < J1; ++j) acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[j], acc[m][j], 0, 0, 0);
+            }
+        }
+    }
+}
+
 // in / out / skip: split activations (header).  Wl: this layer's region-4 weights.  grid = ceil(n / 8) * F / 128, block 512.
 // Pipeline: stage s+1 (the next tap group's weights, and with the first tap group of a chunk that chunk's activations) is
 // in flight as LDS-DMA into the other buffer while stage s is computed; ONE barrier per stage (it also drains this wave's
@@ -137,7 +190,8 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
                                                           const unsigned char* skip, const uint8_t* __restrict__ active, int n, int F,
                                                           unsigned* __restrict__ flag, const uint32_t* __restrict__ n_ptr RAZ_STAMP_PARAM) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the row-half tests below are scalar branches
     RAZ_STAMP_BEGIN;
     if (n_ptr) n = (int)*n_ptr < n ? (int)*n_ptr : n;   // rows 0..n-1 of a compacted batch (raz_leaf_cache.hip): the count lives on the device
     const int noct = F / OCT, nchunks = F / 16;
@@ -146,37 +200,35 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
     const int b = blockIdx.x;
     const int ot = (b >> 3) % noct;
     const int pg = (b / (8 * noct)) * 8 + (b & 7);
-    const int p0 = pg * NWAVE, pos = p0 + wv;
+    const int p0 = pg * NWAVE, pos = p0 + wv;   // pos: the position whose activations this wave MOVES (it computes for four)
     if (p0 >= n) return;
-    const bool live = pos < n && (!active || active[pos]);
     const size_t pos_bytes = (size_t)F * 256;
     const unsigned char* in_pos = in + (size_t)(pos < n ? pos : n - 1) * pos_bytes;
-    if (tid < 160) {   // the zero rows of both images
-        const int im = tid / 80, k = tid % 80;
+    if (tid < 2 * (Z_BYTES / 16)) {   // the zero areas of both images
+        const int im = tid / (Z_BYTES / 16), k = tid % (Z_BYTES / 16);
         ((f32x4*)(lds + LDS_ACT + im * ACT_IMG + Z_OFF))[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    // per-lane LDS byte offsets (inside an activation image) of the B operand for the 9 taps x 2 square tiles
-    const int kg = lane >> 5;
-    uint32_t boff[2][9];
+    // the wave's tile (header): waves w and w + 4 share a SIMD, so a SIMD holds one wave of each row half
+    const int half = wv >> 2, grp = (wv >> 1) & 1, oh = wv & 1;
+    // per-lane LDS byte offsets (inside an activation image) of the B operand for dx = -1, 0, +1, at board row 4 half - 1 (the row
+    // tile 0 reads under dy = -1; for the top half it does not exist and is never read).  A file off the board reads the zero area
+    // at the bank class of the slot it would have read.
+    const int kg = lane >> 5, colpos = grp * 4 + ((lane & 31) >> 3), x = lane & 7;
+    uint32_t boff[3];
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        const int sq = nt * 32 + (lane & 31), y = sq >> 3, x = sq & 7;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-            const bool ok = yy >= 0 && yy < 8 && xx >= 0 && xx < 8;
-            const int s2 = sq + (t / 3 - 1) * 8 + (t % 3 - 1);
-            boff[nt][t] = ok ? (uint32_t)(wv * ACT_POS + kg * 2048 + s2 * 16) : (uint32_t)(Z_OFF + (s2 & 15) * 16);
-        }
+    for (int t = 0; t < 3; ++t) {
+        const int xx = x + t - 1;
+        const int at = act_pos_off(colpos) + kg * 2048 + ((4 * half - 1) * 8 + xx) * 16;
+        boff[t] = xx >= 0 && xx < 8 ? (uint32_t)at : (uint32_t)(Z_OFF + (at & 255));
     }
-    const uint32_t aoff = (uint32_t)(kg * 4096 + (lane & 31) * 16);   // + tap*8192 + hl*2048 + mtile*512 inside a weight stage
-    f32x16 acc[4][2];
+    const uint32_t aoff = (uint32_t)(kg * 4096 + oh * 1024 + (lane & 31) * 16);   // + tap*8192 + hl*2048 + mtile*512 inside a weight stage
+    f32x16 acc[2][4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m)
+    for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][nt][r] = 0.f;
+            for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
     const unsigned char* wsrc = Wl + (size_t)ot * nchunks * 3 * W_STAGE + lane * 16;
     const unsigned char* asrc = in_pos + lane * 16;
     // stage `st` = (chunk st / 3, tap group st % 3): 24 weight pieces of 1 KiB (3 per wave) + with tap group 0 this wave's
@@ -197,7 +249,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
         }
         if (tg == 0) {
             const unsigned char* a = asrc + (size_t)c * ACT_POS;
-            unsigned char* ad = lds + LDS_ACT + (c & 1) * ACT_IMG + wv * ACT_POS;
+            unsigned char* ad = lds + LDS_ACT + (c & 1) * ACT_IMG + act_pos_off(wv);
 #pragma unroll
             for (int pl = 0; pl < 4; pl += SPLIT ? 1 : 2) GLDS16(a + pl * 1024, ad + pl * 1024);
         }
@@ -214,80 +266,64 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
             if (tg < 2) issue(c, tg + 1);
             else if (c + 1 < nchunks) issue(c + 1, 0);
             const uint32_t wbase = (uint32_t)(LDS_W + (st & 1) * W_STAGE) + aoff;
-#pragma unroll
-            for (int tt = 0; tt < 3; ++tt) {
-                const int t = tg * 3 + tt;
-                if constexpr (SPLIT) {
-                    h8 bh[2], bl[2];
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) {
-                        bh[nt] = *(const h8*)(lds + abase + boff[nt][t]);
-                        bl[nt] = *(const h8*)(lds + abase + boff[nt][t] + 1024);
-                    }
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const h8 ah = *(const h8*)(lds + wbase + tt * 8192 + m * 512);
-                        const h8 al = *(const h8*)(lds + wbase + tt * 8192 + m * 512 + 2048);
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) {
-                            acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[nt], acc[m][nt], 0, 0, 0);
-                            acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[nt], acc[m][nt], 0, 0, 0);
-                            acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[nt], acc[m][nt], 0, 0, 0);
-                        }
-                    }
-                } else {
-                    h8 bh[2];
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) bh[nt] = *(const h8*)(lds + abase + boff[nt][t]);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const h8 ah = *(const h8*)(lds + wbase + tt * 8192 + m * 512);
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) acc[m][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[nt], acc[m][nt], 0, 0, 0);
-                    }
-                }
+            // dy = -1 of board row 0 and dy = +1 of board row 7 are whole all-zero B operands: not read, not issued
+            // (the row that may be skipped is a pass of its own over the stage's taps: only its two accumulators cross the branch)
+            if (tg == 0) {
+                conv_stage<SPLIT, 0, 1, 4>(lds, wbase, abase, boff, acc);
+                if (half != 0) conv_stage<SPLIT, 0, 0, 1>(lds, wbase, abase, boff, acc);
+            } else if (tg == 1) {
+                conv_stage<SPLIT, 1, 0, 4>(lds, wbase, abase, boff, acc);
+            } else {
+                conv_stage<SPLIT, 2, 0, 3>(lds, wbase, abase, boff, acc);
+                if (half != 1) conv_stage<SPLIT, 2, 3, 4>(lds, wbase, abase, boff, acc);
             }
         }
     }
     RAZ_STAMP_AT(2);
-    if (!live) return;
+    // epilogue.  D layout: column = lane & 31 = (position, file) inside tile j, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel in
+    // the 32-tile: a lane holds channels 4 kg .. 4 kg + 3 of every 8-channel group, for its column of the four board rows.  The halves
+    // of the wave trade (halves_trade) tiles 2 k and 2 k + 1: afterwards lane l holds all 8 channels of its column in board row
+    // 4 half + 2 k + kg, one whole 16-byte unit of the layout per plane, so a wave reads and writes 128-byte runs (the 8 files of a
+    // row) of its four positions' planes.  The arithmetic per element is what it always was.
+    const int lpos = p0 + colpos;   // the position this lane's column belongs to
+    const bool live = lpos < n && (!active || active[lpos]);
+    if (!__any(live)) return;
     const float inv_scale = *inv_scale_ptr;
-    // epilogue.  D layout: column = lane & 31 = square inside tile nt, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = channel in the
-    // 32-tile: a lane holds channels 4 kg .. 4 kg + 3 of every 8-channel group, for the squares lane & 31 and 32 + (lane & 31).  The
-    // halves of the wave trade (halves_trade): afterwards lane l holds all 8 channels of square l, one whole 16-byte unit of the
-    // layout per plane, so a wave reads and writes lane-linear 1 KiB planes.  The arithmetic per element is what it always was.
-    unsigned char* out_pos = out + (size_t)pos * pos_bytes + lane * 16;
-    const unsigned char* skip_pos = skip ? skip + (size_t)pos * pos_bytes + lane * 16 : nullptr;
-    // the skip rows of the 32-tile m + 1 are asked for before tile m is computed (out may BE skip: a lane reads exactly the
-    // 16 bytes it overwrites later, so the loads may run ahead of the stores of other units)
+    const size_t lane_off = (size_t)(live ? lpos : p0) * pos_bytes + (size_t)((4 * half + kg) * 8 + x) * 16;   // + k * 256: board row + 2
+    unsigned char* out_pos = out + lane_off;
+    const unsigned char* skip_pos = skip ? skip + lane_off : nullptr;
+    // the skip rows of the next (32-tile, row pair) are asked for before this one is computed (out may BE skip: a lane reads exactly
+    // the 16 bytes it overwrites later, so the loads may run ahead of the stores of other units)
     h8 skh[2][4], skl[2][4];
-    auto load_skip = [&](int m) {
+    auto load_skip = [&](int it) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int oc8 = ot * OCT + m * 32 + q * 8;
-            const size_t unit = (size_t)(oc8 >> 4) * ACT_POS + (size_t)((oc8 >> 3) & 1) * 2048;
-            skh[m & 1][q] = *(const h8*)(skip_pos + unit);
-            if constexpr (SPLIT) skl[m & 1][q] = *(const h8*)(skip_pos + unit + 1024);
+            const int oc8 = ot * OCT + oh * 64 + (it >> 1) * 32 + q * 8;
+            const size_t unit = (size_t)(oc8 >> 4) * ACT_POS + (size_t)((oc8 >> 3) & 1) * 2048 + (size_t)(it & 1) * 256;
+            skh[it & 1][q] = *(const h8*)(skip_pos + unit);
+            if constexpr (SPLIT) skl[it & 1][q] = *(const h8*)(skip_pos + unit + 1024);
         }
     };
-    if (skip_pos) load_skip(0);
+    if (skip_pos && live) load_skip(0);
     bool over = false;
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        if (skip_pos && m + 1 < 4) load_skip(m + 1);
+    for (int it = 0; it < 4; ++it) {   // it = (32-tile m, row pair k)
+        const int m = it >> 1, k = it & 1;
+        if (skip_pos && live && it + 1 < 4) load_skip(it + 1);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int oc8 = ot * OCT + m * 32 + q * 8;   // this lane's 8-channel group (wave-uniform: the bias comes by scalar loads)
-            const size_t unit = (size_t)(oc8 >> 4) * ACT_POS + (size_t)((oc8 >> 3) & 1) * 2048;
+            const int oc8 = ot * OCT + oh * 64 + m * 32 + q * 8;   // this lane's 8-channel group (wave-uniform: the bias comes by scalar loads)
+            const size_t unit = (size_t)(oc8 >> 4) * ACT_POS + (size_t)((oc8 >> 3) & 1) * 2048 + (size_t)k * 256;
             float v[8];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) halves_trade(acc[m][0][q * 4 + j], acc[m][1][q * 4 + j], kg, v[j], v[4 + j]);
+            for (int j = 0; j < 4; ++j) halves_trade(acc[m][2 * k][q * 4 + j], acc[m][2 * k + 1][q * 4 + j], kg, v[j], v[4 + j]);
+            if (!live) continue;   // (after the trade: every lane takes part in it)
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = v[j] * inv_scale + bias[oc8 + j];
             if (skip_pos) {
-                const h8 sh = skh[m & 1][q];
+                const h8 sh = skh[it & 1][q];
                 if constexpr (SPLIT) {
-                    const h8 sl = skl[m & 1][q];
+                    const h8 sl = skl[it & 1][q];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = v[j] + ((float)sh[j] + (float)sl[j]);
                 } else {
@@ -307,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
             if constexpr (SPLIT) *(h8*)(out_pos + unit + 1024) = lo;
         }
     }
-    if (over) flag[(size_t)pos * RAZ_NET_ROWFLAG_WORDS] = 1u;   // an activation beyond the f16 range: this ROW is evaluated again by the exact-f32 kernel (raz_net_repair_rows)
+    if (live && over) flag[(size_t)lpos * RAZ_NET_ROWFLAG_WORDS] = 1u;   // an activation beyond the f16 range: this ROW is evaluated again by the exact-f32 kernel (raz_net_repair_rows)
     RAZ_STAMP_END;
 }
 

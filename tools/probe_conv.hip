@@ -318,7 +318,7 @@ int main(int argc, char** argv) {
                 }
             }
             const double span = (double)(tmax - tmin);
-            const double mfma_cycles_per_wave = 48.0 * 72 * 32;   // issue time of a wave's matrix instructions on its SIMD (2 waves share it)
+            const double mfma_cycles_per_wave = 16.0 * 198 * 32;   // issue time of a wave's matrix instructions on its SIMD (2 waves share it): 216 per chunk less the 18 of the skipped board row
             printf("{\"experiment\": \"stamps\", \"skip_path\": %s, \"positions\": %d, \"launch_ms_event\": %.4f, \"waves_stamped\": %zu, \"cus_seen\": %zu, \"workgroups_per_cu_min_max\": [%zu, %zu], "
                    "\"kernel_span_shader_cycles\": %.0f, \"shader_clock_ghz_from_event_time\": %.3f, \"realtime_ticks_span_100mhz\": %llu, "
                    "\"per_wave_mean_cycles\": {\"start_until_stage0_landed\": %.0f, \"k_loop\": %.0f, \"of_which_inside_barriers\": %.0f, \"epilogue_until_last_store_issued\": %.0f, "
