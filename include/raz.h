@@ -63,6 +63,12 @@ int raz_env_step(uint64_t* black, uint64_t* white, uint8_t* player, uint8_t* sta
                  uint64_t* legal, int action);
 
 /* ---- batched device sweeps: one board per lane over SoA arrays in HBM ----------------------- */
+/* ALIGNMENT.  The kernels move two boards per lane and instruction, so the entries refuse (RAZ_EINVAL, before anything is
+ * launched) arrays that are not aligned as follows; n == 0 returns RAZ_OK without looking at the pointers.
+ *   the uint64_t arrays of raz_legal_moves_batch, raz_calc_flip_batch, raz_step_batch, raz_score_batch, raz_d4_batch: 16 bytes;
+ *   player / status / action of raz_step_batch: 4 bytes (16 bytes for the hybrid form: see raz_sweep_forms);
+ *   pos (raz_calc_flip_batch), sym (raz_d4_batch), winner / diff (raz_score_batch): 2 bytes;
+ *   raz_planes_batch and raz_pick_kth_legal_batch: the natural alignment of the element types. */
 /* find_correct_moves over n boards.  24 B/board. */
 int raz_legal_moves_batch(const uint64_t* own, const uint64_t* enemy, uint64_t* legal, size_t n,
                           raz_stream_t stream);
@@ -71,7 +77,8 @@ int raz_calc_flip_batch(const uint8_t* pos, const uint64_t* own, const uint64_t*
                         uint64_t* flipped, size_t n, raz_stream_t stream);
 /* ReversiEnv.step over n games, in place.  Games whose status[i] != 0 on entry are finished and
  * are left untouched with legal[i] = 0 (the reference's loops never step a done env,
- * worker/self_play.py:155).  action[i] 0..63 or 255 (resign).  45 B/board:
+ * worker/self_play.py:155).  action[i] 0..63 or 255 (resign); any other value names no square and is a move that flips
+ * nothing (the mover loses, status | 0x10, board untouched) on every kernel form.  45 B/board:
  * reads black,white (16) player,status,action (3); writes black,white (16) player,status (2) legal (8). */
 int raz_step_batch(uint64_t* black, uint64_t* white, uint8_t* player, uint8_t* status,
                    uint64_t* legal, const uint8_t* action, size_t n, raz_stream_t stream);
@@ -95,6 +102,11 @@ int raz_planes_batch(const uint64_t* own, const uint64_t* enemy, float* planes, 
  *                      status / action arrays 16-byte aligned - a batch whose arrays are not stays on k_step).
  * For tests and benches that must know what they measured; no device work. */
 int raz_sweep_forms(size_t n, int* legal_moves_form, int* step_form);
+/* The largest grid, in workgroups, any sweep launch takes: 65536, or RAZ_SWEEP_MAXGRID=<workgroups> where that is lower
+ * (TESTS ONLY, read once per process; unset or 0 = 65536: with a cap of 1 or 2 the kernels' grid-stride loops, the prefetch
+ * pipeline of k_legal_moves / k_step and the superblock loops of the sliced kernels take several trips on some thousand boards
+ * instead of 2^18 .. 2^27).  k_step_hybrid's grid is min(superblocks, RAZ_SWEEP_HYBRID_WAVES, this).  No device work. */
+unsigned raz_sweep_max_grid(void);
 /* Uniform random playout driver for tests/benches (test infrastructure shipped with the library,
  * mirrors SURVEY §8(c) "random playout"): action[i] = the k-th set bit of legal[i] where
  * k = rnd[i] % popcount(legal[i]); 255 when legal[i] == 0. */

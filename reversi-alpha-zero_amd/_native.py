@@ -50,6 +50,7 @@ SIGNATURES = {
     "raz_calc_flip_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "raz_step_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "raz_sweep_forms": (c_int, [c_size_t, c_void_p, c_void_p]),
+    "raz_sweep_max_grid": (c_uint32, []),
     "raz_score_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "raz_d4_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "raz_planes_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -126,8 +126,11 @@ RAZ_HD raz_step_result bbv_env_step_first(raz_bb black, raz_bb white, int player
     r.player = (uint8_t)player;
     r.legal = 0;
     const int other_wins = (player == RAZ_PLAYER_BLACK) ? RAZ_WIN_WHITE : RAZ_WIN_BLACK;
-    if (action == RAZ_ACTION_RESIGN) {
-        r.status = (uint8_t)(other_wins | RAZ_STATUS_RESIGNED);
+    if (action >= 64) {
+        // no square of the board: RAZ_ACTION_RESIGN, or (raz_step_batch's contract, include/raz.h) a byte that names none - a move that
+        // flips nothing.  ONE comparison on the way of a real move, as before; bbv_calc_flip must not see such an action: it shifts by it,
+        // and a shift takes the count modulo 64 (the move on square action & 63 would be made)
+        r.status = (uint8_t)(other_wins | (action == RAZ_ACTION_RESIGN ? RAZ_STATUS_RESIGNED : RAZ_STATUS_ILLEGAL));
         return r;
     }
     raz_bb own = (player == RAZ_PLAYER_BLACK) ? black : white;

@@ -27,9 +27,22 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxGrid = 65536;
 
+// The cap in force on every launch of this file.  RAZ_SWEEP_MAXGRID=<workgroups> (tests only, read once per process; unset or 0 = kMaxGrid)
+// lowers it, so that the kernels' loops - k_legal_moves' / k_step's prefetch pipeline, the superblock loops of the sliced kernels, the
+// grid-stride loops of the others - take several trips on batches a test can afford: at kMaxGrid a second trip needs 2^18 (k_planes)
+// to 2^27 (the sliced kernels) boards.
+inline size_t max_grid() {
+    static const size_t v = [] {
+        const char* s = getenv("RAZ_SWEEP_MAXGRID");
+        const size_t g = s && *s ? (size_t)strtoull(s, nullptr, 10) : 0;
+        return g && g < (size_t)kMaxGrid ? g : (size_t)kMaxGrid;
+    }();
+    return v;
+}
+
 inline unsigned grid_for(size_t work_items) {
     size_t g = (work_items + kBlock - 1) / kBlock;
-    if (g > (size_t)kMaxGrid) g = kMaxGrid;
+    if (g > max_grid()) g = max_grid();
     if (g == 0) g = 1;
     return (unsigned)g;
 }
@@ -593,7 +606,7 @@ extern "C" int raz_legal_moves_batch(const uint64_t* own, const uint64_t* enemy,
     // large batches: whole superblocks of 2048 boards on the bit-sliced kernel, the rest on the board-per-lane kernel
     const size_t nsb = n >= sliced_min_boards() ? n / 2048 : 0, done = nsb * 2048;
     if (nsb)
-        hipLaunchKernelGGL(k_legal_moves_sliced, dim3((unsigned)(nsb > (size_t)kMaxGrid ? (size_t)kMaxGrid : nsb)), dim3(64), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_legal_moves_sliced, dim3((unsigned)(nsb > max_grid() ? max_grid() : nsb)), dim3(64), 0, (hipStream_t)stream,
                            (const ulonglong2*)own, (const ulonglong2*)enemy, (ulonglong2*)legal, nsb);
     if (n > done)
         hipLaunchKernelGGL(k_legal_moves, dim3(grid_for((n - done) / 4 + 1)), dim3(kBlock), 0, (hipStream_t)stream,
@@ -627,11 +640,12 @@ extern "C" int raz_step_batch(uint64_t* black, uint64_t* white, uint8_t* player,
     int form = step_form() < 0 ? 2 : step_form();
     if (form == 2 && !(aligned16(player) && aligned16(status) && aligned16(action))) form = 0;
     const size_t nsb = form && n >= sliced_step_min_boards() ? n / 2048 : 0, done = nsb * 2048;
+    const size_t hybrid_grid = hybrid_waves() < max_grid() ? hybrid_waves() : max_grid();
     if (nsb && form == 2)
-        hipLaunchKernelGGL(k_step_hybrid, dim3((unsigned)(nsb > hybrid_waves() ? hybrid_waves() : nsb)), dim3(64), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_step_hybrid, dim3((unsigned)(nsb > hybrid_grid ? hybrid_grid : nsb)), dim3(64), 0, (hipStream_t)stream,
                            (ulonglong2*)black, (ulonglong2*)white, (uchar2*)player, (uchar2*)status, (ulonglong2*)legal, (const uchar2*)action, nsb);
     else if (nsb)
-        hipLaunchKernelGGL(k_step_sliced, dim3((unsigned)(nsb > (size_t)kMaxGrid ? (size_t)kMaxGrid : nsb)), dim3(64), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(k_step_sliced, dim3((unsigned)(nsb > max_grid() ? max_grid() : nsb)), dim3(64), 0, (hipStream_t)stream,
                            (ulonglong2*)black, (ulonglong2*)white, (uchar2*)player, (uchar2*)status, (ulonglong2*)legal, (const uchar2*)action, nsb);
     if (n > done)
         hipLaunchKernelGGL(k_step, dim3(grid_for((n - done) / 4 + 1)), dim3(kBlock), 0, (hipStream_t)stream,
@@ -646,6 +660,8 @@ extern "C" int raz_sweep_forms(size_t n, int* legal_moves_form, int* step_form_o
     *step_form_out = form && n >= sliced_step_min_boards() && n >= 2048 ? form : 0;
     return RAZ_OK;
 }
+
+extern "C" unsigned raz_sweep_max_grid(void) { return (unsigned)max_grid(); }
 
 extern "C" int raz_score_batch(const uint64_t* black, const uint64_t* white, uint8_t* winner,
                                int8_t* diff, size_t n, raz_stream_t stream) {

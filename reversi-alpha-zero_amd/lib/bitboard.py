@@ -100,26 +100,54 @@ def _u64(t):
     return tensor_ptr(t)
 
 
+def _same_batch(entry, **tensors):
+    """The tensors of one batched call, as `name_kind=tensor` with kind u64 / u8 / u32: the kernels get the first tensor's numel() and
+    bare pointers, so everything they would otherwise take on trust is compared here, BEFORE a pointer is taken - the element types
+    (TypeError: an int64 `action` would be read as bytes), then the lengths and the devices (ValueError: a shorter `enemy` would be
+    read past its end).  The first tensor gives the length; `out=` is one of the tensors.  Then, as before: device tensors only."""
+    import torch
+    kinds = {"u64": (torch.int64, torch.uint64), "u8": (torch.uint8,), "u32": (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())}
+    items = [(key.rsplit("_", 1)[0], key.rsplit("_", 1)[1], t) for key, t in tensors.items()]
+    for name, kind, t in items:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{entry}: {name} must be a torch tensor, not {type(t).__name__}")
+        if t.dtype not in kinds[kind]:
+            raise TypeError(f"{entry}: {name} must be {' or '.join(str(d) for d in kinds[kind])}, not {t.dtype}")
+    first_name, _, first = items[0]
+    for name, _, t in items[1:]:
+        if t.numel() != first.numel():
+            raise ValueError(f"{entry}: {name} has {t.numel()} elements, {first_name} has {first.numel()}")
+    for name, _, t in items[1:]:
+        if t.device != first.device:
+            raise ValueError(f"{entry}: {name} is on {t.device}, {first_name} on {first.device}")
+    if not first.is_cuda:
+        raise ValueError("batched bitboard ops are device-only (no CPU fallback)")
+    return first.numel()
+
+
 def legal_moves_batch(own, enemy, out=None):
     import torch
-    out = torch.empty_like(own) if out is None else out
-    check(lib.raz_legal_moves_batch(_u64(own), _u64(enemy), _u64(out), own.numel(),
+    out = torch.empty_like(own) if out is None and isinstance(own, torch.Tensor) else out
+    n = _same_batch("legal_moves_batch", own_u64=own, enemy_u64=enemy, out_u64=out)
+    check(lib.raz_legal_moves_batch(_u64(own), _u64(enemy), _u64(out), n,
                                     current_stream_ptr()), "raz_legal_moves_batch")
     return out
 
 
 def calc_flip_batch(pos, own, enemy, out=None):
     import torch
-    out = torch.empty_like(own) if out is None else out
-    check(lib.raz_calc_flip_batch(tensor_ptr(pos), _u64(own), _u64(enemy), _u64(out), own.numel(),
+    out = torch.empty_like(own) if out is None and isinstance(own, torch.Tensor) else out
+    n = _same_batch("calc_flip_batch", own_u64=own, enemy_u64=enemy, pos_u8=pos, out_u64=out)
+    check(lib.raz_calc_flip_batch(tensor_ptr(pos), _u64(own), _u64(enemy), _u64(out), n,
                                   current_stream_ptr()), "raz_calc_flip_batch")
     return out
 
 
 def step_batch(black, white, player, status, legal, action):
     """In-place ReversiEnv.step over a batch (see include/raz.h raz_step_batch)."""
+    n = _same_batch("step_batch", black_u64=black, white_u64=white, player_u8=player, status_u8=status, legal_u64=legal, action_u8=action)
     check(lib.raz_step_batch(_u64(black), _u64(white), tensor_ptr(player), tensor_ptr(status),
-                             _u64(legal), tensor_ptr(action), black.numel(), current_stream_ptr()),
+                             _u64(legal), tensor_ptr(action), n, current_stream_ptr()),
           "raz_step_batch")
 
 
@@ -132,34 +160,44 @@ def sweep_forms(n):
     return a.value, b.value
 
 
+def sweep_max_grid():
+    """The largest grid, in workgroups, a sweep launch takes (include/raz.h raz_sweep_max_grid: 65536 unless the test-only
+    RAZ_SWEEP_MAXGRID lowers it)."""
+    return int(lib.raz_sweep_max_grid())
+
+
 def score_batch(black, white):
     import torch
-    winner = torch.empty(black.numel(), dtype=torch.uint8, device=black.device)
-    diff = torch.empty(black.numel(), dtype=torch.int8, device=black.device)
+    n = _same_batch("score_batch", black_u64=black, white_u64=white)
+    winner = torch.empty(n, dtype=torch.uint8, device=black.device)
+    diff = torch.empty(n, dtype=torch.int8, device=black.device)
     check(lib.raz_score_batch(_u64(black), _u64(white), tensor_ptr(winner), tensor_ptr(diff),
-                              black.numel(), current_stream_ptr()), "raz_score_batch")
+                              n, current_stream_ptr()), "raz_score_batch")
     return winner, diff
 
 
 def d4_batch(x, sym, out=None):
     import torch
-    out = torch.empty_like(x) if out is None else out
-    check(lib.raz_d4_batch(_u64(x), _u64(out), tensor_ptr(sym), x.numel(), current_stream_ptr()),
+    out = torch.empty_like(x) if out is None and isinstance(x, torch.Tensor) else out
+    n = _same_batch("d4_batch", x_u64=x, sym_u8=sym, out_u64=out)
+    check(lib.raz_d4_batch(_u64(x), _u64(out), tensor_ptr(sym), n, current_stream_ptr()),
           "raz_d4_batch")
     return out
 
 
 def planes_batch(own, enemy):
     import torch
-    out = torch.empty((own.numel(), 2, 8, 8), dtype=torch.float32, device=own.device)
-    check(lib.raz_planes_batch(_u64(own), _u64(enemy), tensor_ptr(out), own.numel(),
+    n = _same_batch("planes_batch", own_u64=own, enemy_u64=enemy)
+    out = torch.empty((n, 2, 8, 8), dtype=torch.float32, device=own.device)
+    check(lib.raz_planes_batch(_u64(own), _u64(enemy), tensor_ptr(out), n,
                                current_stream_ptr()), "raz_planes_batch")
     return out
 
 
 def pick_kth_legal_batch(legal, rnd):
     import torch
-    out = torch.empty(legal.numel(), dtype=torch.uint8, device=legal.device)
-    check(lib.raz_pick_kth_legal_batch(_u64(legal), tensor_ptr(rnd), tensor_ptr(out), legal.numel(),
+    n = _same_batch("pick_kth_legal_batch", legal_u64=legal, rnd_u32=rnd)
+    out = torch.empty(n, dtype=torch.uint8, device=legal.device)
+    check(lib.raz_pick_kth_legal_batch(_u64(legal), tensor_ptr(rnd), tensor_ptr(out), n,
                                        current_stream_ptr()), "raz_pick_kth_legal_batch")
     return out
