@@ -609,6 +609,36 @@ int raz_trainer_create2(int filters, int res_layers, int value_fc, size_t max_ba
                         size_t workspace_bytes, raz_trainer** out, raz_stream_t stream);
 int raz_trainer_precision(const raz_trainer* t);
 
+/* ---- training rows on the device: the self-play outbox as the trainer's packed data set (csrc/raz_replay.hip) ------
+ * The rows raz_emit_game_rows_json writes as text and the `opt` worker reads back (worker/self_play.py:180-194,219-231: black.moves +
+ * white.moves, z by the winner; agent/player.py:166-179: 8 symmetric rows per searched ply, :132,366-385: the saved policy;
+ * worker/optimize.py:214-231: the consumer), without the text: d_own u64[R], d_enemy u64[R], d_policy f32[R][64], d_z i8[R] - the layout
+ * raz_trainer_step takes - bit for bit what json.load and lib/data_helper.pack_game_data make of the files.
+ * Inputs: the arrays raz_engine_pack_records and raz_engine_harvest fill - d_headers [n_games][plies] ply headers of 48 bytes, d_root_n
+ * [n_games][plies][64], d_summary [n_games], d_done (nullable) [n_games] - in game order.  For a game with winner = status & 0x0f:
+ *   rows    8 for every ply j < min(n_plies, plies) with has_row and player 1 or 2; none where d_done is given and d_done[g] == 0;
+ *   order   the plies of player 1 in ply order, then those of player 2; within a ply flip in {0, 1} major, rot in 0..3 minor;
+ *   boards  flip_vertical (if flip), then rot x rotate90, on own and on enemy;
+ *   policy  output square i takes source square policy_permutation(flip, rot)[i] (np.flipud, then np.rot90(k=-rot)) of: with
+ *           save_policy_of_tau_1 or turn < change_tau_turn, (float)((double)n[i] / (double)sum(n)) - the exact integer sum, which may
+ *           pass 2^32, ONE f64 division, one rounding to f32 (sum == 0: the plain division); otherwise 1.0 at the first maximum of n
+ *           (unsigned compare, lowest square on ties) and 0.0 elsewhere;
+ *   z       black's rows +1 / -1 / 0 for winner 1 / 2 / anything else, white's rows the negative.
+ * raz_train_rows_count: d_row_offset u32[n_games + 1] receives the exclusive prefix sum of the games' row counts in game order, the
+ *   total at [n_games]; computed on the device in one fixed order, without atomics.  total_rows (host, nullable) receives the total;
+ *   non-NULL SYNCHRONISES `stream`.  n_games == 0: RAZ_OK, d_row_offset[0] = 0 (the other arrays are not looked at).
+ * raz_train_rows_fill: row d_row_offset[g] + 8 x (rank of the ply in the order above) + flip * 4 + rot.  No row >= capacity_rows is
+ *   touched, in any array, and nothing at all for a game without rows.  Asynchronous on `stream`.  n_games == 0: RAZ_OK.
+ * RAZ_EINVAL with a message and NO launch: a NULL array (d_done excepted), d_headers / d_summary / d_own / d_enemy not 8-byte or
+ * d_root_n / d_row_offset / d_policy not 4-byte aligned, plies == 0, n_games x plies x 8 >= 2^32 (row numbers are 32-bit).  No GPU:
+ * RAZ_EDEVICE. */
+int raz_train_rows_count(const void* d_headers, const raz_game_summary* d_summary, const uint8_t* d_done, uint32_t n_games,
+                         uint32_t plies, uint32_t* d_row_offset, uint64_t* total_rows, raz_stream_t stream);
+int raz_train_rows_fill(const void* d_headers, const uint32_t* d_root_n, const raz_game_summary* d_summary, const uint8_t* d_done,
+                        uint32_t n_games, uint32_t plies, int change_tau_turn, int save_policy_of_tau_1,
+                        const uint32_t* d_row_offset, uint64_t capacity_rows, uint64_t* d_own, uint64_t* d_enemy, float* d_policy,
+                        int8_t* d_z, raz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

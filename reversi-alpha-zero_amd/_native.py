@@ -154,6 +154,10 @@ SIGNATURES.update({
     "raz_trainer_bytes2": (c_size_t, [c_int, c_int, c_int, c_size_t, c_int]),
     "raz_trainer_create2": (c_int, [c_int, c_int, c_int, c_size_t, c_int, c_void_p, c_size_t, POINTER(c_void_p), c_void_p]),
     "raz_trainer_precision": (c_int, [c_void_p]),
+    # training rows from the self-play outbox (csrc/raz_replay.hip)
+    "raz_train_rows_count": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, POINTER(c_uint64), c_void_p]),
+    "raz_train_rows_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_uint64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

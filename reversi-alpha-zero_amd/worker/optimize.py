@@ -33,13 +33,16 @@ def default_device(backend):
     return "cuda:0" if backend == "hip" or torch.cuda.is_available() else "cpu"
 
 
-def start(config, backend=None, seed=0, max_epochs=None, device=None, precision=None):
-    return OptimizeWorker(config, backend=backend or DEFAULT_BACKEND, seed=seed, device=device, precision=precision).start(max_epochs=max_epochs)
+def start(config, backend=None, seed=0, max_epochs=None, device=None, precision=None, replay=None):
+    return OptimizeWorker(config, backend=backend or DEFAULT_BACKEND, seed=seed, device=device, precision=precision,
+                          replay=replay).start(max_epochs=max_epochs)
 
 
 class OptimizeWorker:
-    def __init__(self, config, backend=DEFAULT_BACKEND, seed=0, device=None, precision=None):
-        """precision (backend="hip" alone): "f32" - raznet-train-v1, what None means - or "f16x3", raznet-train-v2."""
+    def __init__(self, config, backend=DEFAULT_BACKEND, seed=0, device=None, precision=None, replay=None):
+        """precision (backend="hip" alone): "f32" - raznet-train-v1, what None means - or "f16x3", raznet-train-v2.
+        replay (a lib/replay.DeviceReplay, or None): the data set is the replay's - the rows the self-play engine left in HBM, packed
+        there - instead of the play_*.json files: no file is read, none is deleted, and the trainer reads the replay's tensors in place."""
         if backend not in ("hip", "torch"):
             raise ValueError(f"backend={backend!r}: 'hip' or 'torch'")
         if precision is not None:
@@ -57,6 +60,9 @@ class OptimizeWorker:
         self.training_count_of_files = Counter()
         self.dataset = None     # the same four arrays over every loaded file
         self._resident = None   # ... as tensors on the trainer's device
+        self.replay = replay
+        self._replay_version = None
+        self._resume = None     # (total steps, callbacks) of the last training() call
         self.lr = None
         self.epoch_counter = 0
         self.last_losses = None
@@ -68,9 +74,14 @@ class OptimizeWorker:
 
     def training(self, max_epochs=None, sleep_sec=10):
         tc = self.config.trainer
-        self.compile_model()
-        total_steps = tc.start_total_steps
-        callbacks = [PerStepCallback(tc.save_model_steps, self.save_current_model, tc.wait_after_save_model_ratio)]
+        if self.replay is not None and self._resume is not None:
+            # a replay's worker is called once per block of games (worker/self_opt.py): it goes on where the last call stopped - the
+            # same trainer (weights, momentum), step count (learning rate schedule) and save cadence
+            total_steps, callbacks = self._resume
+        else:
+            self.compile_model()
+            total_steps = tc.start_total_steps
+            callbacks = [PerStepCallback(tc.save_model_steps, self.save_current_model, tc.wait_after_save_model_ratio)]
         rounds = 0
         while max_epochs is None or rounds < max_epochs:
             self.load_play_data()
@@ -84,6 +95,7 @@ class OptimizeWorker:
             total_steps += self.train_epoch(tc.epoch_to_checkpoint, callbacks)
             self.count_up_training_count_and_delete_self_play_data_files()
             rounds += 1
+            self._resume = (total_steps, callbacks)
         return total_steps
 
     def compile_model(self):
@@ -187,6 +199,12 @@ class OptimizeWorker:
         return 0 if self.dataset is None else len(self.dataset[0])
 
     def load_play_data(self):
+        if self.replay is not None:
+            if self._replay_version != self.replay.version:
+                logger.debug("taking the training dataset from the device replay")
+                self.dataset = self._resident = self.replay.dataset()   # device tensors, as they are: no host copy
+                self._replay_version = self.replay.version
+            return
         filenames = get_game_data_filenames(self.config.resource)
         updated = False
         for filename in filenames:
@@ -225,7 +243,7 @@ class OptimizeWorker:
 
     def count_up_training_count_and_delete_self_play_data_files(self):
         limit = self.config.trainer.delete_self_play_after_number_of_training
-        if not limit:
+        if not limit or self.replay is not None:   # (a replay keeps its own window: there are no files of it to delete)
             return
         for filename in self.loaded_filenames:
             self.training_count_of_files[filename] += 1
