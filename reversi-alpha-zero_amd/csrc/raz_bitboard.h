@@ -155,6 +155,27 @@ RAZ_HD raz_bb bb_calc_flip(int pos, raz_bb own, raz_bb enemy) {
     return f1 | bb_rotate180(f2);
 }
 
+// ---- the net's input planes ------------------------------------------------------------------
+// Tap t = ky * 3 + kx of a 3x3 convolution at square sq reads the square one row (ky - 1) and one
+// file (kx - 1) away: is that square on the board, and (*s, a valid shift count either way) which.
+RAZ_HD bool bb_tap(int sq, int t, int* s) {
+    const int yy = (sq >> 3) + t / 3 - 1, xx = (sq & 7) + t % 3 - 1;
+    *s = (yy * 8 + xx) & 63;
+    return (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
+}
+// The nine tap values of square sq in the own plane (x0) and the enemy plane (x1); off the board 0.
+RAZ_HD void bb_tap_planes(raz_bb own, raz_bb enemy, int sq, float* x0, float* x1) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int t = 0; t < 9; ++t) {
+        int s;
+        const bool ok = bb_tap(sq, t, &s);
+        x0[t] = ok ? (float)((own >> s) & 1) : 0.0f;
+        x1[t] = ok ? (float)((enemy >> s) & 1) : 0.0f;
+    }
+}
+
 // ---- game state machine (env/reversi_env.py) -------------------------------------------------
 // player: 1 = black, 2 = white (Player enum, reversi_env.py:9).
 // status: 0 = running; 1/2/3 = done with Winner black/white/draw (Winner enum, :11);

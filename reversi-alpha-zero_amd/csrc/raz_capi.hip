@@ -5,6 +5,8 @@
 // single positions (ReversiEnv facade, record emission).  They are not a fallback for the batched
 // device paths: every *_batch / engine entry point is device-only and fails with RAZ_EDEVICE when
 // no GPU is present.
+#include <atomic>
+#include <mutex>
 #include <stdio.h>
 #include <string.h>
 #include "raz_bitboard.h"
@@ -27,6 +29,36 @@ int raz_fail_hip(hipError_t e, const char* where) {
 int raz_check_launch(const char* where) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return raz_fail_hip(e, where);
+    return RAZ_OK;
+}
+
+int raz_lds_opt_in(const void* kernel, size_t bytes, const char* where) {
+    // a slot belongs to the first kernel that claims it; granted[d] = the largest limit set for it on device d.  A launch that fits
+    // what was granted only reads; raising the limit is serialised, so that a smaller request cannot land after a larger one.  A
+    // kernel beyond the table or a device beyond it makes the call every time: harmless
+    constexpr int kDevices = 16;
+    struct Slot {
+        std::atomic<const void*> kernel{nullptr};
+        std::atomic<size_t> granted[kDevices];
+    };
+    static Slot slots[32];   // (static storage: granted starts at 0)
+    static std::mutex raising;
+    int dev = 0;
+    RAZ_HIP_TRY(hipGetDevice(&dev), where);
+    Slot* mine = nullptr;
+    for (Slot& c : slots) {
+        const void* k = nullptr;
+        if (c.kernel.compare_exchange_strong(k, kernel, std::memory_order_acq_rel) || k == kernel) {
+            mine = &c;
+            break;
+        }
+    }
+    std::atomic<size_t>* granted = mine && dev >= 0 && dev < kDevices ? &mine->granted[dev] : nullptr;
+    if (granted && bytes <= granted->load(std::memory_order_acquire)) return RAZ_OK;
+    std::lock_guard<std::mutex> lock(raising);
+    if (granted && bytes <= granted->load(std::memory_order_relaxed)) return RAZ_OK;
+    RAZ_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), where);
+    if (granted) granted->store(bytes, std::memory_order_release);
     return RAZ_OK;
 }
 

@@ -136,7 +136,7 @@ int raz_launch_tree_net(const raz_engine_dev& d, bool solver, uint32_t n_steps, 
     // behind the plane buffer: the heads' scratch of a forward, shared in time with backup_leaf's 64 floats and - solver forms only - the
     // scalar end-game search's frames (704 B); 16 waves per CU x 9.7 KB either way
     const int between = 64 + (solver ? (int)(sizeof(SolverLDS) / sizeof(float)) : 0);
-    const int head = 192 + V > between ? 192 + V : between;
+    const int head = (int)heads_lds_floats(V) > between ? (int)heads_lds_floats(V) : between;
     const size_t shm = ((size_t)16 * PS + head) * sizeof(float);
     int rc = RAZ_OK;
     while (n_steps && rc == RAZ_OK) {

@@ -9,6 +9,10 @@ int raz_fail(int code, const char* msg);
 int raz_fail_hip(hipError_t e, const char* where);
 // hipGetLastError() after a launch -> RAZ_OK / RAZ_EDEVICE.
 int raz_check_launch(const char* where);
+// The LDS opt-in: a kernel that takes more than 64 KB of dynamic LDS has its hipFuncAttributeMaxDynamicSharedMemorySize raised to
+// `bytes` before its launch.  The call reaches HIP once per (kernel, device), and again only when `bytes` exceeds what that pair
+// was granted.  RAZ_OK, or RAZ_EDEVICE with the HIP error recorded under `where`.
+int raz_lds_opt_in(const void* kernel, size_t bytes, const char* where);
 
 #define RAZ_HIP_TRY(expr, where)                              \
     do {                                                      \

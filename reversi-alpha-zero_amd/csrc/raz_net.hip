@@ -13,17 +13,18 @@
 // are accumulated at a time in registers; the 3x3 taps read the neighbouring lanes' activations
 // from LDS with an off-board predicate; weights are wave-uniform and pre-arranged as
 // [layer][oc/16][tap][ic][16] so one scalar s_load_dwordx16 feeds 16 fmafs.  Layer 0 reads its
-// input planes straight out of the two bitboards.  This is the right shape for narrow nets
+// input planes straight out of the two bitboards (bb_tap); the heads are raz_net_heads.h over the
+// last activation buffer.  This is the right shape for narrow nets
 // (mini.yml: F=16, R=1) where a GEMM tile would be mostly padding; wide nets (F=256) go to the
 // MFMA kernel.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "raz_bitboard.h"
 #include "raz_detmath.h"
 #include "raz_internal.h"
+#include "raz_net_heads.h"
 #include "raz_net_layout.h"
 
 bool raz_net_mfma_supported(int F, int V);
@@ -76,14 +77,13 @@ __device__ __forceinline__ void net_wave_position(const float* __restrict__ W, N
         head = smem;
     }
     // neighbour index and validity for the 9 taps
-    const int y = lane >> 3, x = lane & 7;
     int nbr[9];
     bool ok[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-        ok[t] = (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
-        nbr[t] = ok[t] ? yy * 8 + xx : lane;
+        int s;
+        ok[t] = bb_tap(lane, t, &s);
+        nbr[t] = ok[t] ? s : lane;
     }
     const int nlayers = 2 * R + 1;
     float* bufs[3] = {buf0, buf1, buf2};
@@ -137,59 +137,11 @@ __device__ __forceinline__ void net_wave_position(const float* __restrict__ W, N
         if (second && !TWO_BUF) ia = (ia + 2) % 3;
     }
     const float* a = bufs[ia];  // trunk output [F][64]
-    const float* H = W + heads_off(F, R);
-    const float* pol_w = H;
-    const float* pol_b = pol_w + 2 * F;
-    const float* pfc_w = pol_b + 2;
-    const float* pfc_b = pfc_w + 128 * 64;
-    const float* val_w = pfc_b + 64;
-    const float* val_b = val_w + F;
-    const float* v1_w = val_b + 1;
-    const float* v1_b = v1_w + 64 * V;
-    const float* v2_w = v1_b + V;
-    const float* v2_b = v2_w + V;
-    float* ph = head;
-    float* vh = head + 128;
-    float* h1 = head + 192;
-    {
-        float p0 = pol_b[0], p1 = pol_b[1], v0 = val_b[0];
-        for (int ic = 0; ic < F; ++ic) {
-            const float xv = a[ic * 64 + lane];
-            p0 = fmaf(xv, pol_w[ic], p0);
-            p1 = fmaf(xv, pol_w[F + ic], p1);
-            v0 = fmaf(xv, val_w[ic], v0);
-        }
-        ph[lane] = p0 > 0.0f ? p0 : 0.0f;
-        ph[64 + lane] = p1 > 0.0f ? p1 : 0.0f;
-        vh[lane] = v0 > 0.0f ? v0 : 0.0f;
-    }
-    __syncthreads();
-    // policy dense 128 -> 64, lane = output square
-    float logit = pfc_b[lane];
+    const HeadWeights h = head_weights(W + heads_off(F, R), F, V);
+    float p0 = h.pol_b[0], p1 = h.pol_b[1], v0 = h.val_b[0];
 #pragma unroll 8
-    for (int j = 0; j < 128; ++j) logit = fmaf(ph[j], pfc_w[j * 64 + lane], logit);
-    float m = logit;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) m = fmaxf(m, __shfl_xor(m, s));
-    const float e = raz_det_expf(logit - m);
-    float sum = e;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) sum = sum + __shfl_xor(sum, s);
-    policy_row[lane] = e / sum;
-    // value dense 64 -> V (relu), lane = hidden unit (loop if V > 64)
-    for (int o0 = 0; o0 < V; o0 += 64) {
-        const int o = o0 + lane;
-        if (o < V) {
-            float acc = v1_b[o];
-#pragma unroll 8
-            for (int j = 0; j < 64; ++j) acc = fmaf(vh[j], v1_w[j * V + o], acc);
-            h1[o] = acc > 0.0f ? acc : 0.0f;
-        }
-    }
-    __syncthreads();
-    float acc = v2_b[0];
-    for (int j = 0; j < V; ++j) acc = fmaf(h1[j], v2_w[j], acc);
-    if (lane == 0) *value_out = raz_det_tanhf(acc);
+    for (int ic = 0; ic < F; ++ic) heads_1x1_step(h, F, ic, a[ic * 64 + lane], p0, p1, v0);
+    heads_finish(h, V, p0, p1, v0, head, lane, policy_row, value_out);
 }
 
 template <bool LDS_ACT>
@@ -243,7 +195,7 @@ extern "C" size_t raz_net_weight_bytes(int filters, int res_layers, int value_fc
 }
 
 static size_t lds_bytes_for(int F, int V, bool lds_act) {
-    return ((lds_act ? (size_t)3 * F * 64 : 0) + 192 + (size_t)V) * sizeof(float);
+    return ((lds_act ? (size_t)3 * F * 64 : 0) + heads_lds_floats(V)) * sizeof(float);
 }
 static bool use_lds(int F, int V) { return lds_bytes_for(F, V, true) <= 64 * 1024; }
 
@@ -270,10 +222,9 @@ extern "C" int raz_net_load(raz_net* net, const void* blob, size_t blob_bytes, v
     const int F = h[2], R = h[3], V = h[4];
     if (F <= 0 || F % 16 || R < 0 || V <= 0)
         return raz_fail(RAZ_EINVAL, "raz_net_load: filters must be a positive multiple of 16");
-    if (V > RAZ_NET_MAX_VALUE_FC)   // the heads' LDS ((192 + V) floats) would pass the default 64 KB a launch may take
+    if (V > RAZ_NET_MAX_VALUE_FC)   // the heads' LDS (heads_lds_floats(V)) would pass the default 64 KB a launch may take
         return raz_fail(RAZ_EINVAL, "raz_net_load: value_fc above RAZ_NET_MAX_VALUE_FC");
-    const size_t nsrc = ((size_t)F * 18 + F) + (size_t)R * 2 * ((size_t)F * F * 9 + F) + (2 * (size_t)F + 2) +
-                        (128 * 64 + 64) + ((size_t)F + 1) + (64 * (size_t)V + V) + ((size_t)V + 1);
+    const size_t nsrc = conv_floats(F, 2) + (size_t)R * 2 * conv_floats(F, F) + heads_floats(F, V);
     if (blob_bytes != 32 + 4 * nsrc) return raz_fail(RAZ_EINVAL, "raz_net_load: blob size mismatch");
     const size_t need = total_floats(F, R, V) * sizeof(float);
     if (d_bytes < need) return raz_fail(RAZ_ENOMEM, "raz_net_load: device weight buffer too small");
@@ -289,8 +240,7 @@ extern "C" int raz_net_load(raz_net* net, const void* blob, size_t blob_bytes, v
         memcpy(w + (size_t)F * 9 * cin, src + (size_t)F * cin * 9, F * sizeof(float));
         src += (size_t)F * cin * 9 + F;
     }
-    const size_t nheads = wave_floats(F, R, V) - heads_off(F, R);
-    memcpy(dst.data() + heads_off(F, R), src, nheads * sizeof(float));
+    memcpy(dst.data() + heads_off(F, R), src, heads_floats(F, V) * sizeof(float));
     {   // region 2: B operands of v_mfma_f32_16x16x4_f32, k = tap*Cin + ic (raz_net_layout.h)
         const float* lsrc = (const float*)((const char*)blob + 32);
         for (int l = 0; l < 2 * R + 1; ++l) {
@@ -376,16 +326,9 @@ extern "C" int raz_net_range_stats(const raz_net* net, int* overflowed, unsigned
 int raz_net_repair_rows(const float* W, int F, int R, int V, const uint64_t* own, const uint64_t* enemy, float* policy, float* value,
                         size_t n, unsigned* rowflag, unsigned* sticky, const uint32_t* list, const uint32_t* n_ptr, hipStream_t s) {
     NetDims d = {F, R, V};
-    const size_t shm = ((size_t)2 * F * 64 + 192 + (size_t)V) * sizeof(float);   // two activation buffers + the heads' scratch
-    {   // 130 KB for F = 256: above the default dynamic limit - raise it once per device (two threads racing here both set it: harmless)
-        static std::atomic<unsigned long long> attr_devices{0};
-        int dev = 0;
-        RAZ_HIP_TRY(hipGetDevice(&dev), "raz_net_forward: hipGetDevice");
-        if (dev >= 64 || !(attr_devices.load(std::memory_order_acquire) >> dev & 1)) {
-            RAZ_HIP_TRY(hipFuncSetAttribute((const void*)k_net_wave_repair, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "raz_net_forward: hipFuncSetAttribute (repair)");
-            if (dev < 64) attr_devices.fetch_or(1ull << dev, std::memory_order_release);
-        }
-    }
+    const size_t shm = ((size_t)2 * F * 64 + heads_lds_floats(V)) * sizeof(float);   // two activation buffers + the heads' scratch
+    // 130 KB for F = 256: above the default dynamic limit
+    if (const int rc = raz_lds_opt_in((const void*)k_net_wave_repair, shm, "raz_net_forward: hipFuncSetAttribute (repair)")) return rc;
     const unsigned grid = n < 256 ? (unsigned)n : 256u;   // one block per CU reads ceil(n / 256) row flags; a flagged row is repaired by the block that found it
     hipLaunchKernelGGL(k_net_wave_repair, dim3(grid), dim3(64), shm, s, W, d, (const raz_bb*)own, (const raz_bb*)enemy, policy, value,
                        (int)n, rowflag, sticky, list, n_ptr);

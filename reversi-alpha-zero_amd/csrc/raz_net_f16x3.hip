@@ -11,7 +11,7 @@
 // shape), NOT bit-identical to the CPU oracle's fmaf chains - the matrix core's internal 16-term summation is not a
 // documented IEEE sequence - so games played on this path are checked against the oracle fed with THIS net's outputs
 // through the reference's own NN seam (ReversiPlayer(api=...), agent/player.py:41).  The first layer (2 planes) and the
-// heads stay exact-f32 VALU chains as in v1.
+// heads (raz_net_heads.h) stay exact-f32 VALU chains as in v1.
 //
 // Activations live in HBM already split, in the order the kernel's LDS image wants them:
 //     [position][16-channel chunk][plane: k-group(8 ch) x {hi, lo} = 4][square 64][8 halfs]      (F*256 bytes per position)
@@ -55,6 +55,7 @@
 #include "raz_bitboard.h"
 #include "raz_detmath.h"
 #include "raz_internal.h"
+#include "raz_net_heads.h"
 #include "raz_net_layout.h"
 
 namespace {
@@ -388,13 +389,11 @@ __global__ __launch_bounds__(256, 6) void k_conv0_split(const float* __restrict_
         bo[1] = own[src];
         be[1] = enemy[src];
     }
-    const int y = lane >> 3, x = lane & 7;
     f32x2 x0[9], x1[9];   // (row A, row B)
 #pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-        const bool ok = (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
-        const int s = (yy * 8 + xx) & 63;
+    for (int t = 0; t < 9; ++t) {   // bb_tap_planes for two rows at once: one predicate and one shift count serve both
+        int s;
+        const bool ok = bb_tap(lane, t, &s);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             x0[t][k] = ok ? (float)(uint32_t)((bo[k] >> s) & 1) : 0.0f;
@@ -451,8 +450,8 @@ __global__ __launch_bounds__(256, 6) void k_conv0_split(const float* __restrict_
     if (overB) flag[(size_t)posB * RAZ_NET_ROWFLAG_WORDS] = 1u;
 }
 
-// Heads as in k_heads_wide (exact f32 chains), reading the trunk output in the split layout: x = hi + lo (exact in f32);
-// !SPLIT (v3): x = hi, the lo planes are not read.
+// Heads (raz_net_heads.h: exact f32 chains), reading the trunk output in the split layout, 16 bytes a load: x = hi + lo (exact in
+// f32); !SPLIT (v3): x = hi, the lo planes are not read.
 template <bool SPLIT>
 __global__ __launch_bounds__(64) void k_heads_split(const float* __restrict__ H, const unsigned char* trunk,
                                                     const uint8_t* __restrict__ active, float* __restrict__ policy,
@@ -463,21 +462,9 @@ __global__ __launch_bounds__(64) void k_heads_split(const float* __restrict__ H,
     if (n_ptr) n = (int)*n_ptr < n ? (int)*n_ptr : n;
     if (pos >= n || (!list && active && !active[pos])) return;
     const size_t dst = list ? list[pos] : (size_t)pos;   // results go back to the leaf-exchange row
-    const float* pol_w = H;
-    const float* pol_b = pol_w + 2 * F;
-    const float* pfc_w = pol_b + 2;
-    const float* pfc_b = pfc_w + 128 * 64;
-    const float* val_w = pfc_b + 64;
-    const float* val_b = val_w + F;
-    const float* v1_w = val_b + 1;
-    const float* v1_b = v1_w + 64 * V;
-    const float* v2_w = v1_b + V;
-    const float* v2_b = v2_w + V;
-    float* ph = head;
-    float* vh = head + 128;
-    float* h1 = head + 192;
+    const HeadWeights h = head_weights(H, F, V);
     const unsigned char* a = trunk + (size_t)pos * F * 256 + lane * 16;
-    float p0 = pol_b[0], p1 = pol_b[1], v0 = val_b[0];
+    float p0 = h.pol_b[0], p1 = h.pol_b[1], v0 = h.val_b[0];
     for (int c = 0; c < F / 16; ++c) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -485,43 +472,11 @@ __global__ __launch_bounds__(64) void k_heads_split(const float* __restrict__ H,
             h8 lo = hi;
             if constexpr (SPLIT) lo = *(const h8*)(a + (size_t)c * ACT_POS + (g * 2 + 1) * 1024);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int ic = c * 16 + g * 8 + j;
-                const float xv = SPLIT ? (float)hi[j] + (float)lo[j] : (float)hi[j];
-                p0 = fmaf(xv, pol_w[ic], p0);
-                p1 = fmaf(xv, pol_w[F + ic], p1);
-                v0 = fmaf(xv, val_w[ic], v0);
-            }
+            for (int j = 0; j < 8; ++j)
+                heads_1x1_step(h, F, c * 16 + g * 8 + j, SPLIT ? (float)hi[j] + (float)lo[j] : (float)hi[j], p0, p1, v0);
         }
     }
-    ph[lane] = p0 > 0.0f ? p0 : 0.0f;
-    ph[64 + lane] = p1 > 0.0f ? p1 : 0.0f;
-    vh[lane] = v0 > 0.0f ? v0 : 0.0f;
-    __syncthreads();
-    float logit = pfc_b[lane];
-#pragma unroll 16
-    for (int j = 0; j < 128; ++j) logit = fmaf(ph[j], pfc_w[j * 64 + lane], logit);
-    float m = logit;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) m = fmaxf(m, __shfl_xor(m, s));
-    const float e = raz_det_expf(logit - m);
-    float sum = e;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) sum = sum + __shfl_xor(sum, s);
-    policy[dst * 64 + lane] = e / sum;
-    for (int o0 = 0; o0 < V; o0 += 64) {
-        const int o = o0 + lane;
-        if (o < V) {
-            float acc = v1_b[o];
-#pragma unroll 8
-            for (int j = 0; j < 64; ++j) acc = fmaf(vh[j], v1_w[j * V + o], acc);
-            h1[o] = acc > 0.0f ? acc : 0.0f;
-        }
-    }
-    __syncthreads();
-    float acc = v2_b[0];
-    for (int j = 0; j < V; ++j) acc = fmaf(h1[j], v2_w[j], acc);
-    if (lane == 0) value[dst] = raz_det_tanhf(acc);
+    heads_finish(h, V, p0, p1, v0, head, lane, policy + dst * 64, value + dst);
 }
 
 }  // namespace
@@ -561,7 +516,7 @@ void raz_net_build_f16x3(const float* src, float* dst, int F, int R, int V) {
 static int heads_launch(bool split, const float* W, int F, int R, int V, const unsigned char* trunk, const uint8_t* active, float* policy,
                         float* value, size_t n, hipStream_t s, const uint32_t* list, const uint32_t* n_ptr) {
     const auto heads = split ? k_heads_split<true> : k_heads_split<false>;
-    hipLaunchKernelGGL(heads, dim3((unsigned)n), dim3(64), (192 + (size_t)V) * sizeof(float), s,
+    hipLaunchKernelGGL(heads, dim3((unsigned)n), dim3(64), heads_lds_floats(V) * sizeof(float), s,
                        W + heads_off(F, R), trunk, active, policy, value, (int)n, F, V, list, n_ptr);
     return raz_check_launch("raz_net_forward (split heads)");
 }
@@ -602,15 +557,8 @@ int raz_net_forward_f16x3(const float* W, int F, int R, int V, const uint64_t* o
     unsigned* flag = (unsigned*)(bufT + (size_t)n * F * 256);   // per-row range flags
     const float* scales = W + f16x3_scale_off(F, R, V);
     const auto conv = split ? k_conv3x3_f16x3<true> : k_conv3x3_f16x3<false>;   // (v3 keeps v2's LDS image, lo halves unused)
-    {   // the kernel's LDS image exceeds the default dynamic limit: raise it once per device and kernel
-        static unsigned long long attr_devices[2] = {0, 0};   // [split] bit d = done on device d (one process drives one device; a second one still gets its call)
-        int dev = 0;
-        RAZ_HIP_TRY(hipGetDevice(&dev), "raz_net_forward: hipGetDevice");
-        if (dev >= 64 || !(attr_devices[split] >> dev & 1)) {
-            RAZ_HIP_TRY(hipFuncSetAttribute((const void*)conv, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES), "raz_net_forward: hipFuncSetAttribute");
-            if (dev < 64) attr_devices[split] |= 1ull << dev;
-        }
-    }
+    // the kernel's LDS image exceeds the default dynamic limit
+    if (const int rc = raz_lds_opt_in((const void*)conv, LDS_BYTES, "raz_net_forward: hipFuncSetAttribute")) return rc;
     const unsigned conv_threads = NWAVE * 64;
     const auto conv0 = split ? k_conv0_split<true> : k_conv0_split<false>;
     hipLaunchKernelGGL(conv0, dim3((unsigned)((n + CONV0_ROWS - 1) / CONV0_ROWS)), dim3(256), 0, s, W + conv_off(F, 0), (const raz_bb*)own,

@@ -15,9 +15,30 @@ RAZ_HD_LAYOUT size_t conv_off(int F, int l) {
     return l == 0 ? 0 : conv_floats(F, 2) + (size_t)(l - 1) * conv_floats(F, F);
 }
 RAZ_HD_LAYOUT size_t heads_off(int F, int R) { return conv_off(F, 2 * R + 1); }
-RAZ_HD_LAYOUT size_t wave_floats(int F, int R, int V) {
-    return heads_off(F, R) + (2 * (size_t)F + 2) + (128 * 64 + 64) + ((size_t)F + 1) + (64 * (size_t)V + V) + ((size_t)V + 1);
+// The heads, as in the blob: policy 1x1 conv (2 x F + 2), policy dense (128 x 64 + 64), value 1x1 conv (F + 1), value dense
+// (64 x V + V), value output (V + 1).  head_weights is the one carving of them; heads_floats is where it ends.
+struct HeadWeights {
+    const float *pol_w, *pol_b, *pfc_w, *pfc_b, *val_w, *val_b, *v1_w, *v1_b, *v2_w, *v2_b;
+};
+RAZ_HD_LAYOUT HeadWeights head_weights(const float* H, int F, int V) {
+    HeadWeights h;
+    h.pol_w = H;
+    h.pol_b = h.pol_w + 2 * F;
+    h.pfc_w = h.pol_b + 2;
+    h.pfc_b = h.pfc_w + 128 * 64;
+    h.val_w = h.pfc_b + 64;
+    h.val_b = h.val_w + F;
+    h.v1_w = h.val_b + 1;
+    h.v1_b = h.v1_w + 64 * V;
+    h.v2_w = h.v1_b + V;
+    h.v2_b = h.v2_w + V;
+    return h;
 }
+RAZ_HD_LAYOUT constexpr size_t heads_floats(int F, int V) { return (2 * (size_t)F + 2) + (128 * 64 + 64) + ((size_t)F + 1) + (64 * (size_t)V + V) + ((size_t)V + 1); }
+// LDS scratch of the heads of one position: ph[128] (policy planes) vh[64] (value plane) h1[V] (value hidden layer)
+constexpr int HEAD_VH = 128, HEAD_H1 = 192;
+RAZ_HD_LAYOUT constexpr size_t heads_lds_floats(int V) { return HEAD_H1 + (size_t)V; }
+RAZ_HD_LAYOUT size_t wave_floats(int F, int R, int V) { return heads_off(F, R) + heads_floats(F, V); }
 RAZ_HD_LAYOUT int mfma_ksteps(int F, int l) { return l == 0 ? 5 : 9 * F / 4; }
 RAZ_HD_LAYOUT size_t mfma_layer_floats(int F, int l) { return (size_t)(F / 16) * mfma_ksteps(F, l) * 64; }
 RAZ_HD_LAYOUT size_t mfma_off(int F, int R, int V) { return (wave_floats(F, R, V) + 63) / 64 * 64; }
@@ -43,7 +64,7 @@ RAZ_HD_LAYOUT size_t wide_tile_off(int F, int R, int V, int l, int c, int nt) { 
 RAZ_HD_LAYOUT bool f16x3_supported(int F) { return F >= 128 && F % 128 == 0; }
 // raznet-forward-v2 repairs a row out of the f16 range in the same forward only where the row's f32 activations (two buffers) and
 // the heads' scratch fit the 160 KB of LDS of a CU (k_net_wave_repair); elsewhere such a row only raises the sticky flag
-RAZ_HD_LAYOUT bool f16x3_repairs(int F, int V) { return ((size_t)2 * F * 64 + 192 + (size_t)V) * 4 <= 160 * 1024; }
+RAZ_HD_LAYOUT bool f16x3_repairs(int F, int V) { return ((size_t)2 * F * 64 + heads_lds_floats(V)) * 4 <= 160 * 1024; }
 RAZ_HD_LAYOUT size_t f16x3_off(int F, int R, int V) { return (wide_off(F, R, V) + (size_t)2 * R * wide_layer_floats(F) + 63) / 64 * 64; }
 RAZ_HD_LAYOUT size_t f16x3_layer_off(int F, int R, int V, int l) { return f16x3_off(F, R, V) + (size_t)(l - 1) * wide_layer_floats(F); }  // l >= 1
 RAZ_HD_LAYOUT size_t f16x3_scale_off(int F, int R, int V) { return f16x3_off(F, R, V) + (size_t)2 * R * wide_layer_floats(F); }

@@ -14,13 +14,14 @@
 // halo (zero) so there is no predicate in the k-loop, every tap/channel variation is an immediate
 // offset of one per-lane base address, and the D fragment (4 consecutive squares of one channel
 // per lane) is written with one aligned ds_write_b128.  Two buffers: `a` (block input, updated in
-// place by the residual add) and `t`.
+// place by the residual add) and `t`.  The heads over `a` are net_heads_tuned (raz_net_wave.h);
+// F = 32 has the same body written out (see there).
 #include <hip/hip_runtime.h>
 #include "raz_bitboard.h"
 #include "raz_detmath.h"
 #include "raz_internal.h"
 #include "raz_net_layout.h"
-#include "raz_net_wave.h"   // plane layout, conv_layer, the in-wave forward
+#include "raz_net_wave.h"   // plane layout, conv_layer, the heads (net_heads_tuned), the in-wave forward
 
 namespace {
 
@@ -50,20 +51,7 @@ __global__ __launch_bounds__(64, F == 16 ? 2 : 1) void k_net_mfma(const float* _
         for (int j = lane; j < NBUF * F * PS / 4; j += 64) z[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     __syncthreads();
-    const float* H = W + heads_off(F, R);
-    const float* pol_w = H;
-    const float* pol_b = pol_w + 2 * F;
-    const float* pfc_w = pol_b + 2;
-    const float* pfc_b = pfc_w + 128 * 64;
-    const float* val_w = pfc_b + 64;
-    const float* val_b = val_w + F;
-    const float* v1_w = val_b + 1;
-    const float* v1_b = v1_w + 64 * V;
-    const float* v2_w = v1_b + V;
-    const float* v2_b = v2_w + V;
-    float* ph = head;
-    float* vh = head + 128;
-    float* h1 = head + 192;
+    const HeadWeights h = head_weights(W + heads_off(F, R), F, V);
     constexpr bool HOIST = (F == 16);
     const bool pre = HOIST && R == 1;
     float w0[5], w1[HOIST ? 36 : 1], w2[HOIST ? 36 : 1], pb0 = 0.f, pb1 = 0.f, pb2 = 0.f;
@@ -108,69 +96,72 @@ __global__ __launch_bounds__(64, F == 16 ? 2 : 1) void k_net_mfma(const float* _
             }
         }
         RAZ_NET_TICK(3);
-        {
-            const float* a = bufA + pidx(lane);
-            float p0 = pol_b[0], p1 = pol_b[1], v0 = val_b[0];
+        if constexpr (F == 32) {
+            // net_heads_tuned written out.  Through the shared function this one instantiation compiled to another kernel - 119
+            // instead of 183 VGPRs, the trunk's weight loads on immediate offsets - and ran 5.6 % slower (32x2x32 net, 65 536
+            // positions: 4.57 -> 4.83 ms, profiles/r13/net_mfma_forward_ab.json); F = 16 and F = 64 keep their kernels either way.
+            // Keep the two bodies the same, operation for operation.
+            const float* ph = head;
+            const float* vh = head + HEAD_VH;
+            float* h1 = head + HEAD_H1;
+            {
+                const float* a = bufA + pidx(lane);
+                float p0 = h.pol_b[0], p1 = h.pol_b[1], v0 = h.val_b[0];
 #pragma unroll 8
-            for (int ic = 0; ic < F; ++ic) {
-                const float xv = a[ic * PS];
-                p0 = fmaf(xv, pol_w[ic], p0);
-                p1 = fmaf(xv, pol_w[F + ic], p1);
-                v0 = fmaf(xv, val_w[ic], v0);
+                for (int ic = 0; ic < F; ++ic) heads_1x1_step(h, F, ic, a[ic * PS], p0, p1, v0);
+                heads_relu_1x1(head, lane, p0, p1, v0);
             }
-            ph[lane] = p0 > 0.0f ? p0 : 0.0f;
-            ph[64 + lane] = p1 > 0.0f ? p1 : 0.0f;
-            vh[lane] = v0 > 0.0f ? v0 : 0.0f;
-        }
-        __syncthreads();
-        RAZ_NET_TICK(4);
-        // policy dense 128 -> 64, lane = output: all 128 weight loads are issued before the chain
-        float logit = pfc_b[lane];
+            __syncthreads();
+            RAZ_NET_TICK(4);
+            float logit = h.pfc_b[lane];
 #pragma unroll 1
-        for (int j0 = 0; j0 < 128; j0 += 32) {  // 32 loads in flight, then their 32 chained fmas
-            float wv[32];
+            for (int j0 = 0; j0 < 128; j0 += 32) {
+                float wv[32];
 #pragma unroll
-            for (int j = 0; j < 32; ++j) wv[j] = pfc_w[(j0 + j) * 64 + lane];
+                for (int j = 0; j < 32; ++j) wv[j] = h.pfc_w[(j0 + j) * 64 + lane];
 #pragma unroll
-            for (int j = 0; j < 32; ++j) logit = fmaf(ph[j0 + j], wv[j], logit);
-        }
-        RAZ_NET_TICK(5);
-        // softmax: max (order-free) and the xor-butterfly sum (1,2,4,8 inside a row by DPP; the 16/32
-        // steps are (r0+r1)+(r2+r3) of the four row sums)
-        float m = logit;
-        m = fmaxf(m, dppf<0xB1>(m));
-        m = fmaxf(m, dppf<0x4E>(m));
-        m = fmaxf(m, dppf<0x141>(m));
-        m = fmaxf(m, dppf<0x140>(m));
-        m = fmaxf(fmaxf(lanef(m, 0), lanef(m, 16)), fmaxf(lanef(m, 32), lanef(m, 48)));
-        const float e = raz_det_expf(logit - m);
-        float sum = e;
-        sum = sum + dppf<0xB1>(sum);
-        sum = sum + dppf<0x4E>(sum);
-        sum = sum + dppf<0x141>(sum);
-        sum = sum + dppf<0x140>(sum);
-        sum = (lanef(sum, 0) + lanef(sum, 16)) + (lanef(sum, 32) + lanef(sum, 48));
-        policy[(size_t)pos * 64 + lane] = e / sum;
-        RAZ_NET_TICK(6);
-        for (int o0 = 0; o0 < V; o0 += 64) {
-            const int o = o0 + lane;
-            if (o < V) {
-                float acc = v1_b[o];
+                for (int j = 0; j < 32; ++j) logit = fmaf(ph[j0 + j], wv[j], logit);
+            }
+            RAZ_NET_TICK(5);
+            float m = logit;
+            m = fmaxf(m, dppf<0xB1>(m));
+            m = fmaxf(m, dppf<0x4E>(m));
+            m = fmaxf(m, dppf<0x141>(m));
+            m = fmaxf(m, dppf<0x140>(m));
+            m = fmaxf(fmaxf(lanef(m, 0), lanef(m, 16)), fmaxf(lanef(m, 32), lanef(m, 48)));
+            const float e = raz_det_expf(logit - m);
+            float sum = e;
+            sum = sum + dppf<0xB1>(sum);
+            sum = sum + dppf<0x4E>(sum);
+            sum = sum + dppf<0x141>(sum);
+            sum = sum + dppf<0x140>(sum);
+            sum = (lanef(sum, 0) + lanef(sum, 16)) + (lanef(sum, 32) + lanef(sum, 48));
+            policy[(size_t)pos * 64 + lane] = e / sum;
+            RAZ_NET_TICK(6);
+            for (int o0 = 0; o0 < V; o0 += 64) {
+                const int o = o0 + lane;
+                if (o < V) {
+                    float acc = h.v1_b[o];
 #pragma unroll 1
-                for (int j0 = 0; j0 < 64; j0 += 32) {
-                    float wv[32];
+                    for (int j0 = 0; j0 < 64; j0 += 32) {
+                        float wv[32];
 #pragma unroll
-                    for (int j = 0; j < 32; ++j) wv[j] = v1_w[(j0 + j) * V + o];
+                        for (int j = 0; j < 32; ++j) wv[j] = h.v1_w[(j0 + j) * V + o];
 #pragma unroll
-                    for (int j = 0; j < 32; ++j) acc = fmaf(vh[j0 + j], wv[j], acc);
+                        for (int j = 0; j < 32; ++j) acc = fmaf(vh[j0 + j], wv[j], acc);
+                    }
+                    h1[o] = acc > 0.0f ? acc : 0.0f;
                 }
-                h1[o] = acc > 0.0f ? acc : 0.0f;
             }
+            __syncthreads();
+            float acc = h.v2_b[0];
+            for (int j = 0; j < V; ++j) acc = fmaf(h1[j], h.v2_w[j], acc);
+            if (lane == 0) value[pos] = raz_det_tanhf(acc);
+        } else {
+            float val;
+            net_heads_tuned<F, false>(h, V, bufA, head, lane, policy[(size_t)pos * 64 + lane], val, [&](int k) { RAZ_NET_TICK(k); });
+            if (lane == 0) value[pos] = val;
         }
-        __syncthreads();
-        float acc = v2_b[0];
-        for (int j = 0; j < V; ++j) acc = fmaf(h1[j], v2_w[j], acc);
-        if (lane == 0) value[pos] = raz_det_tanhf(acc);
         RAZ_NET_TICK(7);
         __syncthreads();  // the next position overwrites bufT / head
     }
@@ -179,21 +170,15 @@ __global__ __launch_bounds__(64, F == 16 ? 2 : 1) void k_net_mfma(const float* _
 template <int F>
 int launch(const float* W, int R, int V, const raz_bb* own, const raz_bb* enemy, const uint8_t* active,
            float* policy, float* value, size_t n, hipStream_t s, unsigned long long* prof) {
-    const size_t shm = ((size_t)2 * F * PS + 192 + V) * sizeof(float);
-    if (shm > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_net_mfma<F, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return raz_fail_hip(e, "raz_net_forward: hipFuncSetAttribute");
-    }
+    const size_t shm = ((size_t)2 * F * PS + heads_lds_floats(V)) * sizeof(float);
+    const auto kernel = prof ? k_net_mfma<F, true> : k_net_mfma<F, false>;
+    if (shm > 64 * 1024)   // (F = 64)
+        if (const int rc = raz_lds_opt_in((const void*)kernel, shm, "raz_net_forward: hipFuncSetAttribute")) return rc;
     unsigned maxgrid = 2048;  // LDS-limited residency: 16 (F=16) / 8 workgroups per CU
     if (const char* g = getenv("RAZ_NET_MAXGRID"))   // tests only: fewer workgroups, so that each one loops over several positions
         if (atoi(g) > 0) maxgrid = (unsigned)atoi(g);
     const unsigned grid = (unsigned)(n < maxgrid ? n : maxgrid);
-    if (prof)
-        hipLaunchKernelGGL((k_net_mfma<F, true>), dim3(grid), dim3(64), shm, s, W, R, V, own, enemy, active, policy,
-                           value, (int)n, prof);
-    else
-        hipLaunchKernelGGL((k_net_mfma<F, false>), dim3(grid), dim3(64), shm, s, W, R, V, own, enemy, active, policy,
-                           value, (int)n, prof);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), shm, s, W, R, V, own, enemy, active, policy, value, (int)n, prof);
     return raz_check_launch("raz_net_forward (mfma)");
 }
 

@@ -1,11 +1,12 @@
 // raz_net_wave.h — device code shared by the narrow-net kernels (raz_net_mfma.hip) and the fused tree + net kernel of the
-// engine (raz_engine.hip k_tree_net): the zero-haloed LDS plane layout, one 3x3 conv layer on v_mfma_f32_16x16x4_f32, and the
-// whole forward pass of ONE position of an F == 16 net by ONE wave (raz_net16_forward_in_wave).  Everything here computes
-// raznet-forward-v1: every output one k-ordered fmaf chain, bit-identical to the CPU oracle.
+// engine (raz_engine.hip k_tree_net): the zero-haloed LDS plane layout, one 3x3 conv layer on v_mfma_f32_16x16x4_f32, the tuned
+// form of the heads (net_heads_tuned), and the whole forward pass of ONE position of an F == 16 net by ONE wave
+// (raz_net16_forward_in_wave).  Everything here computes raznet-forward-v1: every output one k-ordered fmaf chain, bit-identical to the CPU oracle.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "raz_bitboard.h"
 #include "raz_detmath.h"
+#include "raz_net_heads.h"
 #include "raz_net_layout.h"
 
 namespace {
@@ -137,15 +138,87 @@ __device__ __forceinline__ void conv_layer(const float* __restrict__ Wl, const f
         __syncthreads();
 }
 
+// The heads of ONE position on ONE wave (lane = board square) over the trunk's output in the zero-haloed `planes`: the chains of
+// raz_net_heads.h, tuned for the kernels where the heads are a large share of a position's time - the dense layers keep 32 weight
+// loads in flight ahead of their 32 chained fmas, and the softmax's max (order-free) and xor-butterfly sum take the steps 1, 2, 4, 8
+// inside a row by DPP, the steps 16 / 32 as (r0 + r1) + (r2 + r3) of the four row sums.  WAVE_SYNC: the LDS hand-overs are
+// wave_lds_sync() (a single wave inside a larger kernel) instead of the workgroup barrier.  tick(4), (5), (6) mark the ends of
+// the 1x1 convolutions, the policy dense layer and the softmax (RAZ_NET_PROF; nothing elsewhere).  Every lane receives the value.
+template <int F, bool WAVE_SYNC, class Tick>
+__device__ __forceinline__ void net_heads_tuned(const HeadWeights& h, int V, const float* planes, float* head, int lane,
+                                                float& policy_of_lane, float& value, Tick tick) {
+    auto sync = [] {
+        if (WAVE_SYNC)
+            wave_lds_sync();
+        else
+            __syncthreads();
+    };
+    const float* ph = head;
+    const float* vh = head + HEAD_VH;
+    float* h1 = head + HEAD_H1;
+    {
+        const float* a = planes + pidx(lane);
+        float p0 = h.pol_b[0], p1 = h.pol_b[1], v0 = h.val_b[0];
+#pragma unroll 8
+        for (int ic = 0; ic < F; ++ic) heads_1x1_step(h, F, ic, a[ic * PS], p0, p1, v0);
+        heads_relu_1x1(head, lane, p0, p1, v0);
+    }
+    sync();
+    tick(4);
+    float logit = h.pfc_b[lane];
+#pragma unroll 1
+    for (int j0 = 0; j0 < 128; j0 += 32) {
+        float wv[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) wv[j] = h.pfc_w[(j0 + j) * 64 + lane];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) logit = fmaf(ph[j0 + j], wv[j], logit);
+    }
+    tick(5);
+    float m = logit;
+    m = fmaxf(m, dppf<0xB1>(m));
+    m = fmaxf(m, dppf<0x4E>(m));
+    m = fmaxf(m, dppf<0x141>(m));
+    m = fmaxf(m, dppf<0x140>(m));
+    m = fmaxf(fmaxf(lanef(m, 0), lanef(m, 16)), fmaxf(lanef(m, 32), lanef(m, 48)));
+    const float e = raz_det_expf(logit - m);
+    float sum = e;
+    sum = sum + dppf<0xB1>(sum);
+    sum = sum + dppf<0x4E>(sum);
+    sum = sum + dppf<0x141>(sum);
+    sum = sum + dppf<0x140>(sum);
+    sum = (lanef(sum, 0) + lanef(sum, 16)) + (lanef(sum, 32) + lanef(sum, 48));
+    policy_of_lane = e / sum;
+    tick(6);
+    for (int o0 = 0; o0 < V; o0 += 64) {
+        const int o = o0 + lane;
+        if (o < V) {
+            float acc = h.v1_b[o];
+#pragma unroll 1
+            for (int j0 = 0; j0 < 64; j0 += 32) {
+                float wv[32];
+#pragma unroll
+                for (int j = 0; j < 32; ++j) wv[j] = h.v1_w[(j0 + j) * V + o];
+#pragma unroll
+                for (int j = 0; j < 32; ++j) acc = fmaf(vh[j0 + j], wv[j], acc);
+            }
+            h1[o] = acc > 0.0f ? acc : 0.0f;
+        }
+    }
+    sync();
+    float acc = h.v2_b[0];
+    for (int j = 0; j < V; ++j) acc = fmaf(h1[j], h.v2_w[j], acc);
+    value = raz_det_tanhf(acc);
+}
 
 // The forward pass of ONE position of an F == 16 net by the calling wave, for a kernel that already runs one wave per game
-// (k_tree_net).  `buf`: 16 * PS + 192 + V floats of LDS owned by this wave whose first 16 * PS floats were zeroed once
+// (k_tree_net).  `buf`: 16 * PS + heads_lds_floats(V) floats of LDS owned by this wave whose first 16 * PS floats were zeroed once
 // (raz_net16_lds_floats / raz_net16_zero_planes; the halos must read as 0, the interiors are overwritten for every position).
 // The trunk runs in place in that single plane buffer (conv_layer<.., INPLACE>), the layers' B operands are fetched from L2
 // when the layer starts (no registers stay resident between positions: the caller's own state has to fit beside this in 128
 // VGPRs for 4 waves per SIMD).  Returns the policy entry of square `lane` and the value.  Same operations in the same order as
 // k_net_mfma: bit-identical.
-__host__ __device__ inline constexpr int raz_net16_lds_floats(int V) { return 16 * PS + 192 + V; }
+__host__ __device__ inline constexpr int raz_net16_lds_floats(int V) { return 16 * PS + (int)heads_lds_floats(V); }
 __device__ __forceinline__ void raz_net16_zero_planes(float* buf, int lane) {
     f32x4* z = (f32x4*)buf;
     for (int j = lane; j < 16 * PS / 4; j += 64) z[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -154,21 +227,7 @@ __device__ __forceinline__ void raz_net16_zero_planes(float* buf, int lane) {
 __device__ __forceinline__ void raz_net16_forward_in_wave(const float* __restrict__ W, int R, int V, raz_bb bo, raz_bb be, float* buf,
                                                           int lane, float& policy_of_lane, float& value) {
     constexpr int F = 16;
-    float* head = buf + F * PS;  // ph[128] vh[64] h1[V]
-    const float* H = W + heads_off(F, R);
-    const float* pol_w = H;
-    const float* pol_b = pol_w + 2 * F;
-    const float* pfc_w = pol_b + 2;
-    const float* pfc_b = pfc_w + 128 * 64;
-    const float* val_w = pfc_b + 64;
-    const float* val_b = val_w + F;
-    const float* v1_w = val_b + 1;
-    const float* v1_b = v1_w + 64 * V;
-    const float* v2_w = v1_b + V;
-    const float* v2_b = v2_w + V;
-    float* ph = head;
-    float* vh = head + 128;
-    float* h1 = head + 192;
+    const HeadWeights h = head_weights(W + heads_off(F, R), F, V);
     buf[pidx(lane)] = (float)((bo >> lane) & 1ULL);       // the two input bit planes: planes 0/1
     buf[PS + pidx(lane)] = (float)((be >> lane) & 1ULL);
     wave_lds_sync();
@@ -188,63 +247,7 @@ __device__ __forceinline__ void raz_net16_forward_in_wave(const float* __restric
                                                           lane, dummyK, 0.f, frag, true);
         }
     }
-    {
-        const float* a = buf + pidx(lane);
-        float p0 = pol_b[0], p1 = pol_b[1], v0 = val_b[0];
-#pragma unroll 8
-        for (int ic = 0; ic < F; ++ic) {
-            const float xv = a[ic * PS];
-            p0 = fmaf(xv, pol_w[ic], p0);
-            p1 = fmaf(xv, pol_w[F + ic], p1);
-            v0 = fmaf(xv, val_w[ic], v0);
-        }
-        ph[lane] = p0 > 0.0f ? p0 : 0.0f;
-        ph[64 + lane] = p1 > 0.0f ? p1 : 0.0f;
-        vh[lane] = v0 > 0.0f ? v0 : 0.0f;
-    }
-    wave_lds_sync();
-    float logit = pfc_b[lane];
-#pragma unroll 1
-    for (int j0 = 0; j0 < 128; j0 += 32) {  // 32 loads in flight, then their 32 chained fmas
-        float wv[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) wv[j] = pfc_w[(j0 + j) * 64 + lane];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) logit = fmaf(ph[j0 + j], wv[j], logit);
-    }
-    float m = logit;
-    m = fmaxf(m, dppf<0xB1>(m));
-    m = fmaxf(m, dppf<0x4E>(m));
-    m = fmaxf(m, dppf<0x141>(m));
-    m = fmaxf(m, dppf<0x140>(m));
-    m = fmaxf(fmaxf(lanef(m, 0), lanef(m, 16)), fmaxf(lanef(m, 32), lanef(m, 48)));
-    const float e = raz_det_expf(logit - m);
-    float sum = e;
-    sum = sum + dppf<0xB1>(sum);
-    sum = sum + dppf<0x4E>(sum);
-    sum = sum + dppf<0x141>(sum);
-    sum = sum + dppf<0x140>(sum);
-    sum = (lanef(sum, 0) + lanef(sum, 16)) + (lanef(sum, 32) + lanef(sum, 48));
-    policy_of_lane = e / sum;
-    for (int o0 = 0; o0 < V; o0 += 64) {
-        const int o = o0 + lane;
-        if (o < V) {
-            float acc = v1_b[o];
-#pragma unroll 1
-            for (int j0 = 0; j0 < 64; j0 += 32) {
-                float wv[32];
-#pragma unroll
-                for (int j = 0; j < 32; ++j) wv[j] = v1_w[(j0 + j) * V + o];
-#pragma unroll
-                for (int j = 0; j < 32; ++j) acc = fmaf(vh[j0 + j], wv[j], acc);
-            }
-            h1[o] = acc > 0.0f ? acc : 0.0f;
-        }
-    }
-    wave_lds_sync();
-    float acc = v2_b[0];
-    for (int j = 0; j < V; ++j) acc = fmaf(h1[j], v2_w[j], acc);
-    value = raz_det_tanhf(acc);
+    net_heads_tuned<F, true>(h, V, buf, buf + F * PS, lane, policy_of_lane, value, [](int) {});
     wave_lds_sync();  // the next position overwrites the planes / head
 }
 

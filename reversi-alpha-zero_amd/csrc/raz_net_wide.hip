@@ -16,11 +16,13 @@
 //                (~1 GB per layer at n = 8192 against 0.62 TFLOP: firmly MFMA-bound);
 //                weights (9 F^2 floats per layer) are re-read from L2 by every workgroup
 //   epilogue   = (+ skip) , relu, coalesced 128-byte row segments (lane = square)
-// Layer 0 (2 input planes straight from the bitboards) and the heads are small VALU kernels.
+// Layer 0 (2 input planes straight from the bitboards: bb_tap_planes) and the heads (raz_net_heads.h, fed from HBM) are small
+// VALU kernels.
 #include <hip/hip_runtime.h>
 #include "raz_bitboard.h"
 #include "raz_detmath.h"
 #include "raz_internal.h"
+#include "raz_net_heads.h"
 #include "raz_net_layout.h"
 
 namespace {
@@ -115,16 +117,8 @@ __global__ __launch_bounds__(64) void k_conv0_wide(const float* __restrict__ W0,
     const int pos = blockIdx.x, lane = threadIdx.x;
     if (pos >= n || (active && !active[pos])) return;
     const raz_bb bo = own[pos], be = enemy[pos];
-    const int y = lane >> 3, x = lane & 7;
     float x0[9], x1[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
-        const bool ok = (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
-        const int s = (yy * 8 + xx) & 63;
-        x0[t] = ok ? (float)((bo >> s) & 1) : 0.0f;
-        x1[t] = ok ? (float)((be >> s) & 1) : 0.0f;
-    }
+    bb_tap_planes(bo, be, lane, x0, x1);
     const float* bias = W0 + (size_t)F * 18;
     for (int ocb = 0; ocb < F / 16; ++ocb) {
         float acc[16];
@@ -143,63 +137,19 @@ __global__ __launch_bounds__(64) void k_conv0_wide(const float* __restrict__ W0,
     }
 }
 
-// Heads: 1x1 convs, dense layers, softmax, tanh.  One wave per position over the trunk output in HBM.
+// Heads (raz_net_heads.h): one wave per position over the trunk output in HBM.
 __global__ __launch_bounds__(64) void k_heads_wide(const float* __restrict__ H, const float* trunk,
                                                    const uint8_t* __restrict__ active, float* __restrict__ policy,
                                                    float* __restrict__ value, int n, int F, int V) {
     extern __shared__ __attribute__((aligned(16))) float head[];  // ph[128] vh[64] h1[V]
     const int pos = blockIdx.x, lane = threadIdx.x;
     if (pos >= n || (active && !active[pos])) return;
-    const float* pol_w = H;
-    const float* pol_b = pol_w + 2 * F;
-    const float* pfc_w = pol_b + 2;
-    const float* pfc_b = pfc_w + 128 * 64;
-    const float* val_w = pfc_b + 64;
-    const float* val_b = val_w + F;
-    const float* v1_w = val_b + 1;
-    const float* v1_b = v1_w + 64 * V;
-    const float* v2_w = v1_b + V;
-    const float* v2_b = v2_w + V;
-    float* ph = head;
-    float* vh = head + 128;
-    float* h1 = head + 192;
+    const HeadWeights h = head_weights(H, F, V);
     const float* a = trunk + (size_t)pos * F * 64 + lane;
-    float p0 = pol_b[0], p1 = pol_b[1], v0 = val_b[0];
+    float p0 = h.pol_b[0], p1 = h.pol_b[1], v0 = h.val_b[0];
 #pragma unroll 8
-    for (int ic = 0; ic < F; ++ic) {
-        const float xv = a[(size_t)ic * 64];
-        p0 = fmaf(xv, pol_w[ic], p0);
-        p1 = fmaf(xv, pol_w[F + ic], p1);
-        v0 = fmaf(xv, val_w[ic], v0);
-    }
-    ph[lane] = p0 > 0.0f ? p0 : 0.0f;
-    ph[64 + lane] = p1 > 0.0f ? p1 : 0.0f;
-    vh[lane] = v0 > 0.0f ? v0 : 0.0f;
-    __syncthreads();
-    float logit = pfc_b[lane];
-#pragma unroll 16
-    for (int j = 0; j < 128; ++j) logit = fmaf(ph[j], pfc_w[j * 64 + lane], logit);
-    float m = logit;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) m = fmaxf(m, __shfl_xor(m, s));
-    const float e = raz_det_expf(logit - m);
-    float sum = e;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) sum = sum + __shfl_xor(sum, s);
-    policy[(size_t)pos * 64 + lane] = e / sum;
-    for (int o0 = 0; o0 < V; o0 += 64) {
-        const int o = o0 + lane;
-        if (o < V) {
-            float acc = v1_b[o];
-#pragma unroll 8
-            for (int j = 0; j < 64; ++j) acc = fmaf(vh[j], v1_w[j * V + o], acc);
-            h1[o] = acc > 0.0f ? acc : 0.0f;
-        }
-    }
-    __syncthreads();
-    float acc = v2_b[0];
-    for (int j = 0; j < V; ++j) acc = fmaf(h1[j], v2_w[j], acc);
-    if (lane == 0) value[pos] = raz_det_tanhf(acc);
+    for (int ic = 0; ic < F; ++ic) heads_1x1_step(h, F, ic, a[(size_t)ic * 64], p0, p1, v0);
+    heads_finish(h, V, p0, p1, v0, head, lane, policy + (size_t)pos * 64, value + pos);
 }
 
 }  // namespace
@@ -214,12 +164,7 @@ int raz_net_forward_wide(const float* W, int F, int R, int V, const uint64_t* ow
     float* bufA = (float*)scratch;
     float* bufT = bufA + (size_t)n * F * 64;
     const size_t shm = ((size_t)4 * 16 * PS + KS * 128) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_conv3x3_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return raz_fail_hip(e, "raz_net_forward: hipFuncSetAttribute");
-        attr_set = true;
-    }
+    if (const int rc = raz_lds_opt_in((const void*)k_conv3x3_wide, shm, "raz_net_forward: hipFuncSetAttribute")) return rc;
     hipLaunchKernelGGL(k_conv0_wide, dim3((unsigned)n), dim3(64), 0, s, W + conv_off(F, 0), (const raz_bb*)own,
                        (const raz_bb*)enemy, active, bufA, (int)n, F);
     const dim3 grid((unsigned)((n + 3) / 4), (unsigned)(F / 64));
@@ -232,7 +177,7 @@ int raz_net_forward_wide(const float* W, int F, int R, int V, const uint64_t* ow
                            W + conv_off(F, l2) + (size_t)F * 9 * F, (const float*)bufT, bufA, (const float*)bufA,
                            active, (int)n, F);
     }
-    hipLaunchKernelGGL(k_heads_wide, dim3((unsigned)n), dim3(64), (192 + (size_t)V) * sizeof(float), s,
+    hipLaunchKernelGGL(k_heads_wide, dim3((unsigned)n), dim3(64), heads_lds_floats(V) * sizeof(float), s,
                        W + heads_off(F, R), (const float*)bufA, active, policy, value, (int)n, F, V);
     return raz_check_launch("raz_net_forward (wide)");
 }

@@ -61,16 +61,8 @@ __global__ __launch_bounds__(64) void k_stem_fwd(const float* __restrict__ W /*[
     const int b = blockIdx.x, lane = threadIdx.x;
     const uint32_t row = idx[b];
     const raz_bb bo = own[row], be = enemy[row];
-    const int yy0 = lane >> 3, xx0 = lane & 7;
     float x0[9], x1[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int yy = yy0 + t / 3 - 1, xx = xx0 + t % 3 - 1;
-        const bool ok = (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
-        const int s = (yy * 8 + xx) & 63;
-        x0[t] = ok ? (float)((bo >> s) & 1) : 0.0f;
-        x1[t] = ok ? (float)((be >> s) & 1) : 0.0f;
-    }
+    bb_tap_planes(bo, be, lane, x0, x1);
     for (int oc = 0; oc < F; ++oc) {
         float acc = bias[oc];
         const float* w = W + (size_t)oc * 18;
@@ -87,7 +79,6 @@ __global__ __launch_bounds__(64) void k_stem_wgrad(const float* __restrict__ dy,
                                                    const raz_bb* __restrict__ enemy, const uint32_t* __restrict__ idx,
                                                    const float* __restrict__ W, float* __restrict__ dW, int B, int F, float l2) {
     const int oc = blockIdx.x, lane = threadIdx.x;
-    const int yy0 = lane >> 3, xx0 = lane & 7;
     double acc[18];
 #pragma unroll
     for (int i = 0; i < 18; ++i) acc[i] = 0.0;
@@ -97,9 +88,8 @@ __global__ __launch_bounds__(64) void k_stem_wgrad(const float* __restrict__ dy,
         const double g = (double)dy[((size_t)b * F + oc) * 64 + lane];
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            const int yy = yy0 + t / 3 - 1, xx = xx0 + t % 3 - 1;
-            const bool ok = (yy >= 0) && (yy < 8) && (xx >= 0) && (xx < 8);
-            const int s = (yy * 8 + xx) & 63;
+            int s;
+            const bool ok = bb_tap(lane, t, &s);
             if (ok && ((bo >> s) & 1)) acc[t] = acc[t] + g;
             if (ok && ((be >> s) & 1)) acc[9 + t] = acc[9 + t] + g;
         }

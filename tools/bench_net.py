@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """tools/bench_net.py — MFMA roofline of the net forward alone (the "conv batch" leg of the north
 star): one raz_net_forward over n positions, repeated; prints one JSON line.
-    python tools/bench_net.py [--net ch5|mini] [--n 8192] [--iters 5]"""
+    python tools/bench_net.py [--net ch5|mini | --shape F,R,V] [--n 8192] [--iters 5]"""
 import argparse
 import json
 import os
@@ -14,6 +14,8 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--net", default="ch5", choices=["mini", "ch5"])
+    ap.add_argument("--shape", default=None, metavar="F,R,V",
+                    help="filters, residual blocks and value_fc of a net that has no name here (e.g. 32,2,32), instead of --net")
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--kernel", default=None, choices=["valu", "mfma_wave", "f32", "f16x3", "f16", "auto"],
@@ -26,6 +28,9 @@ def main():
     from reversi_alpha_zero_amd.agent.model import ReversiNet, macs_per_position
     from reversi_alpha_zero_amd.engine import DeviceNet
     F, R, V = {"mini": (16, 1, 16), "ch5": (256, 10, 256)}[args.net]
+    if args.shape:
+        F, R, V = (int(x) for x in args.shape.split(","))
+        args.net = args.shape
     dev = torch.device("cuda:0")
     net = DeviceNet(ReversiNet(F, R, V).keras_init_(0).to_blob(), dev, kernel=args.kernel)
     rng = np.random.default_rng(0)
