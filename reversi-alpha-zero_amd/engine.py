@@ -624,10 +624,23 @@ def raw_from_packed(headers_u8, root_n_i32, summary_u8):
     hdr = np.ascontiguousarray(headers_u8).view(PLY_HEADER).reshape(headers_u8.shape[0], headers_u8.shape[1])
     sm = np.ascontiguousarray(summary_u8).view(GAME_SUMMARY).reshape(-1)
     return dict(headers=hdr, root_n=np.ascontiguousarray(root_n_i32).view(np.uint32), root_w=None,
-                n_plies=sm["n_plies"].copy(), status=sm["status"].copy(),
-                resigned=np.stack([sm["resigned_black"], sm["resigned_white"]], axis=1),
-                game_id=sm["game_id"].copy(), enable_resign=sm["enable_resign"].copy(), sims=sm["sims"].copy(),
+                **bookkeeping_from_summaries(sm), sims=sm["sims"].copy(),
                 final_black=sm["final_black"].copy(), final_white=sm["final_white"].copy())
+
+
+def bookkeeping_from_summaries(summary_u8):
+    """What the worker's resignation bookkeeping (BatchedSelfPlayWorker.bookkeep_raw) reads of finished games, from their 32-byte
+    summaries alone ([n, 32] u8, or GAME_SUMMARY records): raw_from_packed's n_plies, status, resigned, game_id, enable_resign."""
+    sm = np.ascontiguousarray(summary_u8).view(GAME_SUMMARY).reshape(-1)
+    return dict(n_plies=sm["n_plies"].copy(), status=sm["status"].copy(),
+                resigned=np.stack([sm["resigned_black"], sm["resigned_white"]], axis=1),
+                game_id=sm["game_id"].copy(), enable_resign=sm["enable_resign"].copy())
+
+
+def packed_to_host(pk):
+    """Packed DEVICE records (SelfPlayEngine.pack_records, an outbox of play_continuous, or a cut of one: tensors under "headers",
+    "root_n", "summary") copied to the host in read_raw's shape."""
+    return raw_from_packed(*(pk[k].cpu().numpy() for k in ("headers", "root_n", "summary")))
 
 
 def saved_policy(root_n, turn, change_tau_turn, save_policy_of_tau_1):

@@ -12,8 +12,6 @@ the reference's own consumers.  One rank: world > 1 is refused.
 import os
 from logging import getLogger
 
-import numpy as np
-
 logger = getLogger(__name__)
 
 
@@ -28,7 +26,7 @@ def start(config, games_in_flight=None, backend="hip", precision=None, write_fil
     if _world() > 1:
         raise ValueError(f"self_opt runs one process on one GPU (WORLD_SIZE={_world()}): run the `self` and `opt` workers for more")
     import torch
-    from ..engine import GAME_SUMMARY, raw_from_packed
+    from ..engine import bookkeeping_from_summaries, packed_to_host
     from ..lib.replay import DeviceReplay
     from .optimize import OptimizeWorker
     from .self_play import (BatchedSelfPlayWorker, default_block_games, load_model, read_as_int, try_reload_model,
@@ -51,24 +49,13 @@ def start(config, games_in_flight=None, backend="hip", precision=None, write_fil
     local_idx, blocks = 1, 0
     while total_blocks is None or blocks < total_blocks:
         # ---- play
-        packed = player.play_block_continuous(game_idx)
-        if not player._net.range_ok():   # an activation left the f16 range of the split-operand trunk: the block is void (self_play.run)
-            if player._f32_fallback:
-                raise RuntimeError("the net left its numeric range on the exact-f32 kernels too")
-            logger.warning(f"the block at game index {game_idx} is played again on the exact-f32 kernels, which this net stays on")
-            del packed
-            player._f32_fallback = True
-            player._drop_engine(net_too=True)
-            packed = player.play_block_continuous(game_idx)
-        pk = packed(None)
-        del packed
+        # (a block during which the net left the f16 range of the split-operand trunk is void: played again on the exact-f32 kernels)
+        pk = player.play_block_in_range(game_idx, player.play_block_continuous)()
         # ---- store: the rows stay in HBM; the host sees 32 bytes per game (the resignation bookkeeping)
         replay.add(pk["headers"], pk["root_n"], pk["summary"])
-        sm = np.ascontiguousarray(pk["summary"].cpu().numpy()).view(GAME_SUMMARY).reshape(-1)
-        player.bookkeep_raw(dict(n_plies=sm["n_plies"], status=sm["status"], game_id=sm["game_id"], enable_resign=sm["enable_resign"],
-                                 resigned=np.stack([sm["resigned_black"], sm["resigned_white"]], axis=1)))
+        player.bookkeep_raw(bookkeeping_from_summaries(pk["summary"].cpu().numpy()))
         if write_files:
-            player.write_raw(raw_from_packed(*(pk[k].cpu().numpy() for k in ("headers", "root_n", "summary"))), local_idx)
+            player.write_raw(packed_to_host(pk), local_idx)
         del pk
         game_idx += blk
         local_idx += blk

@@ -153,28 +153,34 @@ def plies_for_ggf(headers, n_plies):
             zip(h["action"].tolist(), h["player"].tolist(), h["flags"].tolist(), h["q"].tolist(), h["n"].tolist())]
 
 
-RAW_KEYS = ("headers", "root_n", "n_plies", "status", "resigned", "game_id", "enable_resign", "final_black", "final_white")
+# ---- a block of finished games, from HBM to rank 0 -----------------------------------------------------
+class Block:
+    """The finished games of ONE rank's block while they are still in HBM: the id-ordered outbox of a block played with
+    continuous batching (SelfPlayEngine.play_continuous), or the engine whose slots hold a stepped batch's records
+    (SelfPlayEngine.pack_records).  Calling it cuts the records: block(plies, first_row, rows) -> {"headers": [n, plies, 48] u8,
+    "root_n": [n, plies, 64] i32, "summary": [n, 32] u8} device tensors of rows [first_row, first_row + rows) (default: to the
+    block's end), `plies` None = their longest game - what gather_packed wants as its `packed`.  It holds the outbox / the
+    engine: drop it once the block is collected."""
 
+    def __init__(self, ids, outbox=None, engine=None):
+        self.ids = ids          # game ids per rank in this block = rows
+        self._outbox, self._engine = outbox, engine
 
-def gather_raw(raw, rank, world, device=None):
-    """The single collective of the path on the engine's own record arrays: every rank's arrays (same shapes
-    on all ranks) gathered on rank 0 and concatenated in rank order = global game id order.  Returns None
-    on the other ranks."""
-    import torch
-    import torch.distributed as dist
-    backend = dist.get_backend()
-    dev = torch.device(device) if device is not None else (
-        torch.device("cuda", torch.cuda.current_device()) if backend == "nccl" else torch.device("cpu"))
-    out = {}
-    for k in RAW_KEYS:
-        a = np.ascontiguousarray(raw[k])
-        t = torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev)
-        lst = [torch.empty_like(t) for _ in range(world)] if rank == 0 else None
-        dist.gather(t, lst, dst=0)
-        if rank == 0:
-            parts = [x.cpu().numpy().view(a.dtype).reshape(a.shape) for x in lst]
-            out[k] = np.concatenate(parts, axis=0)
-    return out if rank == 0 else None
+    def __call__(self, plies=None, first_row=0, rows=None):
+        end = self.ids if rows is None else first_row + rows
+        if self._engine is not None:
+            return self._engine.pack_records(first_row, end - first_row, plies)
+        ob = self._outbox
+        if plies is None:   # n_plies is the u32 at byte 20 of a raz_game_summary
+            import torch
+            plies = max(1, int(ob["summary"][first_row:end, 20:24].contiguous().view(torch.int32).max().item())) if first_row < end else 1
+        return {"headers": ob["headers"][first_row:end, :plies].contiguous(), "root_n": ob["root_n"][first_row:end, :plies].contiguous(),
+                "summary": ob["summary"][first_row:end]}
+
+    def to_host(self, plies=None, first_row=0, rows=None):
+        """The same cut copied to the host, in SelfPlayEngine.read_raw's shape (what bookkeep_raw and write_raw read)."""
+        from ..engine import packed_to_host
+        return packed_to_host(self(plies, first_row, rows))
 
 
 def gather_packed(packed, rank, world):
@@ -183,7 +189,7 @@ def gather_packed(packed, rank, world):
     xGMI under the nccl backend; under gloo (CPU test rig) the tensors are staged through host memory - and
     concatenated in rank order = global game id order.  One all_reduce(MAX) of the ply extent first, so that every
     rank packs to the same shape.  Returns (raw dict in read_raw's shape, bytes moved) on rank 0, (None, bytes) elsewhere.
-    `packed` is a callable plies -> dict so the pack happens once, at the common extent."""
+    `packed` is a callable plies -> dict (a Block) so the pack happens once, at the common extent."""
     import torch
     import torch.distributed as dist
     from ..engine import raw_from_packed
@@ -215,7 +221,7 @@ def gather_summaries(summary, rank, world):
     (None, bytes) elsewhere."""
     import torch
     import torch.distributed as dist
-    from ..engine import GAME_SUMMARY
+    from ..engine import bookkeeping_from_summaries
     dev = summary.device if dist.get_backend() == "nccl" else torch.device("cpu")
     t = summary.contiguous().to(dev)
     lst = [torch.empty_like(t) for _ in range(world)] if rank == 0 else None
@@ -223,9 +229,7 @@ def gather_summaries(summary, rank, world):
     moved = t.numel() * t.element_size() * (world - 1)
     if rank != 0:
         return None, moved
-    sm = np.ascontiguousarray(torch.cat(lst, dim=0).cpu().numpy()).view(GAME_SUMMARY).reshape(-1)
-    return dict(n_plies=sm["n_plies"].copy(), status=sm["status"].copy(), game_id=sm["game_id"].copy(),
-                resigned=np.stack([sm["resigned_black"], sm["resigned_white"]], axis=1), enable_resign=sm["enable_resign"].copy()), moved
+    return bookkeeping_from_summaries(torch.cat(lst, dim=0).cpu().numpy()), moved
 
 
 def wants_fused_tree_net(setting, filters, value_fc, net_reserved, cache_log2, play):
@@ -298,6 +302,24 @@ class BatchedSelfPlayWorker:
         # raznet-forward-v2 reported an activation outside the f16 range: this net runs on the exact-f32 kernels from now on
         # (until the next set_net_blob)
         self._f32_fallback = False
+        # -- what a run leaves behind for its caller (bench.py, the tests) ------------------------------
+        self.last_stats = None             # the engine's statistics of the last block played
+        self.block_stats = []              # per continuous block (the last 64): games, sims, steps, the engine loop's seconds
+        self.bytes_written = 0             # JSON text this worker has put into play files
+        self.run_seconds = {"play": 0.0, "gather_and_copy": 0.0, "bookkeeping": 0.0, "handing_to_the_writer": 0.0}   # rank 0: where run()'s wall time went
+        self.last_writer_busy_seconds = 0.0   # the last run's background writer: seconds it spent writing ...
+        self.last_writer_batches = 0          # ... and batches (blocks, or pieces of streamed emission) it wrote
+        self.last_gather_backend = None    # the backend of the last block's gather (None: no process group) ...
+        self.last_gather_bytes = None      # ... and the bytes it moved to rank 0
+        # -- streamed emission (run(), play_block_continuous) ----------------------------------------------
+        self.stream_piece_games = 0        # games per piece handed to the writer (0: max(1024, games_in_flight)), rounded down to whole files
+        self._streamed_rows = 0            # rows of the current block's outbox already handed to the writer
+        # -- between the blocks of a run -------------------------------------------------------------
+        self._last_file_stamp = None       # the newest play-file name stamp this worker has used (names must sort in game order)
+        self._block_stamps_end = None      # rank 0, per-rank emission: the end of the stamp range handed out for the last block
+        self._said_rank0 = False           # the "ranks span several hosts: rank 0 writes all files" notice is logged once
+        self._block_error = None           # what went wrong playing this rank's block, raised once every rank knows (_all_ranks_state)
+        self._blocks_written_everywhere = 0   # per-rank emission: blocks whose files EVERY rank has on disk (_all_ranks_state)
 
     # -- engine life cycle -------------------------------------------------------------------
     def _series_length(self):
@@ -419,49 +441,41 @@ class BatchedSelfPlayWorker:
         budget = int(free * fraction) - self._fixed_device_bytes(cache_log2) - self.games_in_flight * 64 * NODE_MAX_BYTES
         return max(0, budget) // (self.games_in_flight * per_node)
 
-    def play_batch(self, first_game_idx, n_games=None):
-        """Play global game ids first_game_idx + rank*B .. on this rank.  Returns [(plies, summary)]."""
+    def _play_slots(self, first_game_idx, n_games=None):
+        """One game per slot, stepped until all have ended: global game ids first_game_idx + rank*B .. on this rank (the first n_games
+        slots; default all).  Returns (engine, n): the records are in the engine's slots."""
         n = self.games_in_flight if n_games is None else n_games
         base = first_game_idx + self.rank * self.games_in_flight
-        sims = np.array([decide_simulation_num_per_move(self.config, base + i) for i in range(self.games_in_flight)],
-                        dtype=np.uint32)
+        sims = simulation_nums_of_ids(self.config, base, self.games_in_flight)
         eng = self._get_engine(int(sims.max()))
         r = self._series_length()
         if self._series_pos == 0:
             eng.start(base, sims, n_active=n)
         else:
             eng.next_game(base, sims, n_active=n)   # the slots' trees are kept (reset_mtcs_info_per_game > 1)
-        stats = eng.run(allow_gc=(r == 1))
+        self.last_stats = eng.run(allow_gc=(r == 1))
         self._series_pos = (self._series_pos + 1) % r
-        recs = eng.records(save_policy_of_tau_1=self.config.play_data.save_policy_of_tau_1)
-        self.last_stats = stats
-        return recs
+        return eng, n
+
+    def play_batch(self, first_game_idx, n_games=None):
+        """Play global game ids first_game_idx + rank*B .. on this rank.  Returns [(plies, summary)]."""
+        eng, _ = self._play_slots(first_game_idx, n_games)
+        return eng.records(save_policy_of_tau_1=self.config.play_data.save_policy_of_tau_1)
 
     def play_batch_raw(self, first_game_idx, n_games=None, device_records=False):
         """play_batch without the per-ply Python objects: the engine's record arrays (SelfPlayEngine.read_raw),
         cut to the n games played.  device_records: leave the records in HBM and return (engine, n) - the caller
-        packs / gathers them there (run())."""
-        n = self.games_in_flight if n_games is None else n_games
-        base = first_game_idx + self.rank * self.games_in_flight
-        sims = np.array([decide_simulation_num_per_move(self.config, base + i) for i in range(self.games_in_flight)],
-                        dtype=np.uint32)
-        eng = self._get_engine(int(sims.max()))
-        r = self._series_length()
-        if self._series_pos == 0:
-            eng.start(base, sims, n_active=n)
-        else:
-            eng.next_game(base, sims, n_active=n)
-        self.last_stats = eng.run(allow_gc=(r == 1))
-        self._series_pos = (self._series_pos + 1) % r
+        packs / gathers them there (_play_block)."""
+        eng, n = self._play_slots(first_game_idx, n_games)
         if device_records:
             return eng, n
-        raw = eng.read_raw()
-        return {k: raw[k][:n] for k in RAW_KEYS}
+        return {k: v[:n] for k, v in eng.read_raw().items() if k != "root_w"}
 
-    def play_block_continuous(self, first_game_idx):
+    def play_block_continuous(self, first_game_idx, sink=None):
         """This rank's block of game ids [first + rank * block_games, + block_games) with continuous batching: the slots are
-        refilled with the next id as games finish.  Returns the id-ordered device outbox as a `plies -> packed tensors`
-        callable for gather_packed (cut to the block's longest game, or to the extent the ranks agreed on)."""
+        refilled with the next id as games finish.  Returns the id-ordered device outbox as a Block (cut to the block's longest
+        game, or to the extent the ranks agreed on).  sink(raw, first_row) (optional, streamed emission): takes the finished prefix
+        of the outbox in pieces while the block is played; self._streamed_rows says how far that went."""
         blk = self.block_games
         base = first_game_idx + self.rank * blk
         sims = simulation_nums_of_ids(self.config, base, blk)
@@ -477,13 +491,11 @@ class BatchedSelfPlayWorker:
             chunk = max(16, min(chunk, int(pool) // (4 * int(per_step))))
         # a single-rank worker ships the block's finished PREFIX to the file writer while the block is still played (streamed emission,
         # run()): rows [0, p) of the id-ordered outbox are done, p advancing with the polls; pieces are whole files (no file is cut)
-        sink, self._streamed_rows = getattr(self, "_stream_sink", None), 0
+        self._streamed_rows = 0
         unit = whole_files_block(self.config, 1)
-        piece = max(unit, (int(getattr(self, "stream_piece_games", 0) or max(1024, self.games_in_flight)) // unit) * unit)
+        piece = max(unit, (int(self.stream_piece_games or max(1024, self.games_in_flight)) // unit) * unit)
 
         def ship(steps, done_games, st, ob):
-            import torch
-            from ..engine import raw_from_packed
             at = self._streamed_rows
             if done_games - at < piece:
                 return
@@ -492,26 +504,15 @@ class BatchedSelfPlayWorker:
             n = ((p - at) // piece) * piece
             if n <= 0:
                 return
-            plies = max(1, int(ob["summary"][at:at + n, 20:24].contiguous().view(torch.int32).max().item()))
-            sink(raw_from_packed(*(t.cpu().numpy() for t in (ob["headers"][at:at + n, :plies].contiguous(), ob["root_n"][at:at + n, :plies].contiguous(),
-                                                             ob["summary"][at:at + n]))), at)
+            sink(Block(blk, outbox=ob).to_host(None, at, n), at)
             self._streamed_rows = at + n
         outbox, self.last_stats = eng.play_continuous(base, blk, sims, chunk=chunk, on_chunk=ship if sink is not None else None)
         # per block: what the engine's loop took (bench.py worker_end_to_end_config1 reports the run's blocks, not only the last one)
-        self.block_stats = getattr(self, "block_stats", [])
         st = self.last_stats
         self.block_stats.append({"games": int(st.get("finished_games", blk)), "sims": int(st.get("total_sims", 0)), "steps": int(st.get("steps", 0)),
                                  **{k: float(v) for k, v in (st.get("seconds") or {}).items()}})
         del self.block_stats[:-64]   # (a worker runs for days)
-
-        def packed(plies, first_row=0):
-            """Rows [first_row, block) of the outbox, cut to `plies` (None: their longest game)."""
-            if plies is None:   # n_plies is the u32 at byte 20 of a raz_game_summary
-                import torch
-                plies = max(1, int(outbox["summary"][first_row:, 20:24].contiguous().view(torch.int32).max().item())) if first_row < blk else 1
-            return {"headers": outbox["headers"][first_row:, :plies].contiguous(), "root_n": outbox["root_n"][first_row:, :plies].contiguous(),
-                    "summary": outbox["summary"][first_row:]}
-        return packed
+        return Block(blk, outbox=outbox)
 
     def emit_raw(self, raw, first_local_idx=1, threads=None):
         """emit() on raw record arrays: the same files, with the rows' JSON text produced natively
@@ -540,6 +541,31 @@ class BatchedSelfPlayWorker:
             self._emit_executor, self._emit_executor_threads = cf.ThreadPoolExecutor(max_workers=want), want
         return self._emit_executor
 
+    def _stamp_play_file(self, stamp_base, k):
+        """The name stamp of the k-th play file of a write_raw call: this process's clock - or stamp_base + k microseconds -, kept
+        monotonic against the last stamp used (two files inside one clock tick must still sort in game order)."""
+        last = self._last_file_stamp
+        if stamp_base is not None:
+            now = stamp_base + timedelta(microseconds=k)
+        else:
+            now = datetime.now()
+            if last is not None and now <= last:
+                now = last + timedelta(microseconds=1)
+        self._last_file_stamp = now if last is None else max(now, last)
+        return now
+
+    def _track_and_prune(self, known_files, path):
+        """The sorted listing of play_data_dir after `path` was written - listed the first time (None), tracked from then on - and
+        pruned to max_file_num (remove_play_data).  Returns what is left."""
+        if known_files is None:
+            known_files = get_game_data_filenames(self.config.resource)
+        elif not known_files or known_files[-1] < path:
+            known_files.append(path)
+        elif path not in known_files:   # (per-rank emission: files another rank wrote ahead of this one carry later stamps)
+            import bisect
+            bisect.insort(known_files, path)
+        return self.remove_play_data(known_files)
+
     def write_raw(self, raw, first_local_idx=1, threads=None, ahead=128, stamp_base=None):
         """The files of a batch of finished games (self_play.py:180-207), streamed: the JSON text of at most `ahead`
         games is in flight on the host threads while the games before them are written, so memory stays bounded by
@@ -563,13 +589,14 @@ class BatchedSelfPlayWorker:
         # a finished file is WRITTEN on the host threads too (its text is 0.7 MB per game: one thread writing 64-game files kept the
         # whole worker at 1.3 GB/s on the mini net); names are stamped here, in game order, so the listing sorts as the reference's does
         writes, max_writes = deque(), 8
-        stamped = [0, 0]   # play files, GGF files named from stamp_base so far
+        ggf_stamped = 0   # GGF files named from stamp_base so far
 
         def ggf_stamp():
+            nonlocal ggf_stamped
             if stamp_base is None:
                 return None
-            stamped[1] += 1
-            return stamp_base + timedelta(microseconds=stamped[1] - 1)
+            ggf_stamped += 1
+            return stamp_base + timedelta(microseconds=ggf_stamped - 1)
 
         def put(path, frags):
             with open(path, "wb") as f:
@@ -583,7 +610,7 @@ class BatchedSelfPlayWorker:
 
         def settle(leave):
             while len(writes) > leave:
-                self.bytes_written = getattr(self, "bytes_written", 0) + writes.popleft().result()
+                self.bytes_written += writes.popleft().result()
         for g in range(n):
             while submitted < min(n, g + ahead):
                 futs.append(ex.submit(frag, submitted))
@@ -594,29 +621,14 @@ class BatchedSelfPlayWorker:
             if nrows and (not is_draw or pd.drop_draw_game_rate <= drop_draw_uniform(self.seed, int(game_ids[g]))):
                 self.buffer_json.append(text)
             if local_idx % pd.nb_game_in_file == 0 and self.buffer_json:
-                last = getattr(self, "_last_file_stamp", None)
-                if stamp_base is not None:
-                    now = stamp_base + timedelta(microseconds=stamped[0])
-                    stamped[0] += 1
-                else:
-                    now = datetime.now()
-                    if last is not None and now <= last:   # (two files inside one clock tick must still sort in game order)
-                        now = last + timedelta(microseconds=1)
-                self._last_file_stamp = now if last is None else max(now, last)
+                now = self._stamp_play_file(stamp_base, len(paths))
                 path = os.path.join(rc.play_data_dir, rc.play_data_filename_tmpl % now.strftime("%Y%m%d-%H%M%S.%f"))
                 writes.append(ex.submit(put, path, self.buffer_json))
                 self.buffer_json = []
                 paths.append(path)
-                if known_files is None:
-                    settle(0)   # (the listing must see this batch's first file)
-                    known_files = get_game_data_filenames(rc)
-                elif not known_files or known_files[-1] < path:
-                    known_files.append(path)
-                elif path not in known_files:   # (per-rank emission: files another rank wrote ahead of this one carry later stamps)
-                    import bisect
-                    bisect.insort(known_files, path)
-                settle(0 if pd.max_file_num <= max_writes else max_writes)   # never prune a file that is still being written
-                known_files = self.remove_play_data(known_files)
+                # (the listing must see this batch's first file; and never prune a file that is still being written)
+                settle(0 if known_files is None or pd.max_file_num <= max_writes else max_writes)
+                known_files = self._track_and_prune(known_files, path)
             if pd.enable_ggf_data:
                 wr = (local_idx % pd.nb_game_in_ggf_file == 0) or local_idx <= 5
                 self.save_ggf_data(plies_for_ggf(raw["headers"][g], raw["n_plies"][g]), write=wr, stamp=ggf_stamp() if wr else None)
@@ -713,27 +725,34 @@ class BatchedSelfPlayWorker:
         self.check_and_update_resignation_threshold()
         return paths
 
-    def _play_block(self, game_idx):
-        """This rank's ids of the block that starts at game_idx.  Returns (packed, ids per rank): `packed` is the
-        `plies -> packed device tensors` callable gather_packed wants."""
-        continuous = self.block_games > self.games_in_flight and self._series_length() == 1
-        if continuous:
-            return self.play_block_continuous(game_idx), self.block_games
+    def _continuous(self):
+        """Whether a block is played with continuous batching (more ids than slots, refilled as games finish) - not on a carried tree:
+        the games a slot plays in a row form a series there (_series_length)."""
+        return self.block_games > self.games_in_flight and self._series_length() == 1
+
+    def _ids_per_block(self):
+        """Consecutive game ids ONE rank plays between two gathers (_play_block)."""
+        return self.block_games if self._continuous() else self.games_in_flight
+
+    def _play_block(self, game_idx, sink=None):
+        """This rank's ids of the block that starts at game_idx, as a Block.  sink: see play_block_continuous."""
+        if self._continuous():
+            return self.play_block_continuous(game_idx, sink)
         eng, n = self.play_batch_raw(game_idx, device_records=True)
-        return (lambda plies, eng=eng, n=n: eng.pack_records(0, n, plies)), self.games_in_flight
+        return Block(n, engine=eng)
 
     BLOCK_OK, BLOCK_RANGE, BLOCK_FATAL = 0, 1, 2
 
-    def _play_block_checked(self, game_idx):
-        """_play_block + what became of it on THIS rank: BLOCK_OK; BLOCK_RANGE - the net's range flag is up (a search fed with
-        out-of-range priors may also trip an engine error flag before the block ends: the same event; the block is void either
-        way and is played again on the exact-f32 kernels); BLOCK_FATAL - anything else went wrong (pool / table / records full with
-        the net in range, a HIP error, ...): the exception is kept in self._block_error and raised once every rank knows, so
-        that no rank is left waiting in a collective for one that has gone."""
+    def _play_block_checked(self, game_idx, play):
+        """play(game_idx) -> Block + what became of it on THIS rank: BLOCK_OK; BLOCK_RANGE - the net's range flag is up (a search
+        fed with out-of-range priors may also trip an engine error flag before the block ends: the same event; the block is void
+        either way and is played again on the exact-f32 kernels); BLOCK_FATAL - anything else went wrong (pool / table / records
+        full with the net in range, a HIP error, ...): the exception is kept in self._block_error and raised once every rank knows,
+        so that no rank is left waiting in a collective for one that has gone."""
         self._block_error = None
         try:
-            packed, per_rank = self._play_block(game_idx)
-            return packed, per_rank, (self.BLOCK_OK if self._net.range_ok() else self.BLOCK_RANGE)
+            block = play(game_idx)
+            return block, (self.BLOCK_OK if self._net.range_ok() else self.BLOCK_RANGE)
         except Exception as ex:   # noqa: BLE001 - re-raised by _all_ranks_state on every rank
             in_range = True
             try:
@@ -741,9 +760,29 @@ class BatchedSelfPlayWorker:
             except Exception:   # noqa: BLE001 - the device may be gone: fatal
                 pass
             if isinstance(ex, RuntimeError) and not in_range:
-                return None, 0, self.BLOCK_RANGE
+                return None, self.BLOCK_RANGE
             self._block_error = ex
-            return None, 0, self.BLOCK_FATAL
+            return None, self.BLOCK_FATAL
+
+    def play_block_in_range(self, game_idx, play=None, agree=None):
+        """One block played to the end with the net inside its numeric range: play(game_idx) -> Block (default _play_block), and -
+        when any rank's range flag went up during it (raz_net_range_check) - the block discarded on every rank and played again on
+        the exact-f32 kernels, which the net then stays on (until the next set_net_blob).  agree(state) -> the worst state over all
+        ranks, raising where one of them failed (default _all_ranks_state; run() folds its writers' health in).  Returns the Block."""
+        play, agree = play or self._play_block, agree or self._all_ranks_state
+        block, state = self._play_block_checked(game_idx, play)
+        while agree(state) == self.BLOCK_RANGE:
+            if self._f32_fallback or self._series_length() > 1:
+                raise RuntimeError("the net left its numeric range on the exact-f32 kernels too" if self._f32_fallback else
+                                   "an activation of the net left the f16 range of the split-operand trunk (raznet-forward-v2) "
+                                   "inside a series of games on a carried tree: run the worker with net_kernel='f32'")
+            logger.warning("an activation left the f16 range of the split-operand trunk (raznet-forward-v2): the block at "
+                           f"game index {game_idx} is played again on the exact-f32 kernels, which this net stays on")
+            del block   # (holds the engine / the outbox)
+            self._f32_fallback = True
+            self._drop_engine(net_too=True)
+            block, state = self._play_block_checked(game_idx, play)
+        return block
 
     def _group(self):
         """True when the collectives of the path run: more than one rank, or a process group of one (the nccl path exercised on a
@@ -810,11 +849,6 @@ class BatchedSelfPlayWorker:
         filters = struct.unpack_from("<5i", self.net_blob, 0)[2] if self.net_blob and len(self.net_blob) >= 20 else 256
         return self.net_kernel in ("auto", "f16x3", "f16") and filters >= 128 and filters % 128 == 0
 
-    def _ids_per_block(self):
-        """Consecutive game ids ONE rank plays between two gathers (_play_block)."""
-        continuous = self.block_games > self.games_in_flight and self._series_length() == 1
-        return self.block_games if continuous else self.games_in_flight
-
     def _per_rank_emission(self):
         """Whether every rank writes the files of its own id range (see __init__, `emission`).  A file holds nb_game_in_file
         consecutive games counted from the run's first (self_play.py:186: local index % nb_game_in_file), so a rank's range is a
@@ -825,7 +859,7 @@ class BatchedSelfPlayWorker:
             # ranks on several nodes: each would write into its OWN node's play_data_dir while rank 0's game index and pruning count
             # every file as local, and the optimizer on node 0 would train on 1 / nodes of the games.  Gather everything on
             # rank 0 instead; emission="per_rank" stays available to a caller who knows play_data_dir is one shared file system
-            if not getattr(self, "_said_rank0", False):
+            if not self._said_rank0:
                 self._said_rank0 = True
                 logger.info("emission='auto': the ranks span several hosts (LOCAL_WORLD_SIZE < WORLD_SIZE) - every record is gathered on rank 0, which writes all "
                             "files; pass emission='per_rank' if play_data_dir is one file system shared by all nodes")
@@ -848,7 +882,7 @@ class BatchedSelfPlayWorker:
         microseconds on (write_raw's stamp_base; at most per_rank / nb_game_in_ggf_file + 5 files per rank), so names sort by game
         id across ranks and blocks, and after every file an earlier block or run left."""
         now = datetime.now()
-        for last in (getattr(self, "_block_stamps_end", None), getattr(self, "_last_file_stamp", None)):
+        for last in (self._block_stamps_end, self._last_file_stamp):
             if last is not None and now <= last:
                 now = last + timedelta(microseconds=1)
         self._block_stamps_end = now + timedelta(microseconds=self.world * (per_rank + 8))
@@ -875,9 +909,9 @@ class BatchedSelfPlayWorker:
         (api.py:117-125); its answer - and the weights - are broadcast, so every rank plays a block with the same net.
         A block during which an activation of the split-f16 trunk left the f16 range (raz_net_range_check) is discarded
         on every rank and played again on the exact-f32 kernels, which the net then stays on (include/raz.h)."""
-        import time as _tm
+        import sys
+        from time import monotonic
         import torch.distributed as dist
-        from ..engine import raw_from_packed
         rc = self.config.resource
         if self.rank == 0:
             rc.create_directories()
@@ -891,136 +925,48 @@ class BatchedSelfPlayWorker:
         stream = (background_emit and self.world == 1 and not own_files and self._ids_per_block() > self.games_in_flight
                   and not self._may_replay_block())
         # (pieces of <= a quarter of the slots: the play loop must not wait for the writer - 16 may queue up)
-        writer = _BackgroundWriter(self, depth=16 if stream else 1) if (background_emit and (self.rank == 0 or own_files)) else None
-        inline = {"written": 0, "error": None}   # per-rank emission without the background thread
-        block_game_idx = []                      # rank 0, per-rank emission: the game index after each block
-
-        def written():   # blocks whose files THIS rank has on disk
-            return writer.batches if writer is not None else inline["written"]
-
-        def with_writer(state):
-            """Per-rank emission: a rank whose writer has failed says so in the block state, so that every rank stops with it (raised
-            on that rank alone, the others would wait for it in the next collective)."""
-            if own_files and state != self.BLOCK_FATAL:
-                err = inline["error"] if writer is None else (writer.take_error() if writer.failed else None)
-                if err is not None:
-                    self._block_error = err
-                    return self.BLOCK_FATAL
-            return state
-
-        def advance_game_idx():
-            done = min(self._blocks_written_everywhere, len(block_game_idx))
-            if self.rank == 0 and own_files and done > advance_game_idx.done:
-                advance_game_idx.done = done
-                self._write_game_idx(block_game_idx[done - 1])
-        advance_game_idx.done = 0
+        files = _BlockFiles(self, own_files, background_emit, depth=16 if stream else 1)
         self._blocks_written_everywhere = 0
-
-        def agree(state):
-            """The block state all ranks share (raises on every rank if one of them failed) - and, failed or not, the game index
-            file advanced to the last block the same collective showed on disk everywhere."""
-            try:
-                return self._all_ranks_state(with_writer(state), written())
-            finally:
-                advance_game_idx()
         # The writer thread runs Python between its native calls; the play loop gets the interpreter back only when that thread gives
         # it up - by default every 5 ms, which is half a poll interval of a 16-filter net (bench worker_end_to_end_config1: a block played
         # beside a busy writer took 9.4 s, the first block, with nothing to write yet, 7.5 s).  Hand over every 0.2 ms while run() lasts.
-        import sys as _sys
-        _switch = _sys.getswitchinterval()
-        if writer is not None:
-            _sys.setswitchinterval(min(_switch, 2e-4))
+        switch = sys.getswitchinterval()
+        if files.writer is not None:
+            sys.setswitchinterval(min(switch, 2e-4))
         finished = False
         try:
             while total_games is None or local_idx <= total_games:
-                if until is not None:
-                    stop = [_tm.monotonic() >= until]
-                    if self._group():
-                        dist.broadcast_object_list(stop, src=0)
-                    if stop[0]:
-                        break
-                _t0 = _tm.monotonic()
-                self._stream_sink = (lambda raw, row, _l=local_idx: writer.submit(raw, _l + row, None)) if stream else None
-                packed, per_rank, state = self._play_block_checked(game_idx)
-                _t1 = _tm.monotonic()
-                while agree(state) == self.BLOCK_RANGE:
-                    if self._f32_fallback or self._series_length() > 1:
-                        raise RuntimeError("the net left its numeric range on the exact-f32 kernels too" if self._f32_fallback else
-                                           "an activation of the net left the f16 range of the split-operand trunk (raznet-forward-v2) "
-                                           "inside a series of games on a carried tree: run the worker with net_kernel='f32'")
-                    logger.warning("an activation left the f16 range of the split-operand trunk (raznet-forward-v2): the block at "
-                                   f"game index {game_idx} is played again on the exact-f32 kernels, which this net stays on")
-                    del packed
-                    self._f32_fallback = True
-                    self._drop_engine(net_too=True)
-                    packed, per_rank, state = self._play_block_checked(game_idx)
-                mine = None
-                if own_files:
-                    pk = packed(None)   # cut to THIS rank's longest game: nothing has to agree in shape but the summaries
-                    mine = raw_from_packed(*(pk[k].cpu().numpy() for k in ("headers", "root_n", "summary")))
-                    allraw, self.last_gather_bytes = gather_summaries(pk["summary"], self.rank, self.world)
-                    self.last_gather_backend = dist.get_backend()
-                    del pk
-                elif stream and state == self.BLOCK_OK:
-                    # the rest of the block (what was not shipped while it was played) + every game's summary for the bookkeeping
-                    shipped = int(getattr(self, "_streamed_rows", 0))
-                    pk = packed(None, shipped)
-                    rest = raw_from_packed(*(pk[k].cpu().numpy() for k in ("headers", "root_n", "summary")))
-                    if self._group():   # (a process group of one rank: the summaries take the collective's path, 32 B per game)
-                        allraw, self.last_gather_bytes = gather_summaries(packed(1)["summary"], self.rank, self.world)
-                        self.last_gather_backend = dist.get_backend()
-                    else:
-                        from ..engine import GAME_SUMMARY
-                        sm = np.ascontiguousarray(packed(1)["summary"].cpu().numpy()).view(GAME_SUMMARY).reshape(-1)
-                        allraw = dict(n_plies=sm["n_plies"].copy(), status=sm["status"].copy(), game_id=sm["game_id"].copy(),
-                                      resigned=np.stack([sm["resigned_black"], sm["resigned_white"]], axis=1), enable_resign=sm["enable_resign"].copy())
-                    del pk
-                elif self._group():
-                    allraw, self.last_gather_bytes = gather_packed(packed, self.rank, self.world)
-                    self.last_gather_backend = dist.get_backend()
-                else:
-                    pk = packed(None)
-                    allraw = raw_from_packed(*(pk[k].cpu().numpy() for k in ("headers", "root_n", "summary")))
-                    del pk
-                del packed   # (holds the engine / the outbox: nothing of this block may pin device memory past this point)
-                _t2 = _tm.monotonic()
+                if until is not None and self._deadline_passed(until):
+                    break
+                t0 = monotonic()
+                sink = (lambda raw, row, _l=local_idx: files.writer.submit(raw, _l + row, None)) if stream else None
+                block = self.play_block_in_range(game_idx, lambda idx: self._play_block(idx, sink), files.agree)
+                t1 = monotonic()
+                per_rank = block.ids
+                allraw, mine, first_row = self._collect_block(block, own_files, stream)
+                del block   # (holds the engine / the outbox: nothing of this block may pin device memory past this point)
+                t2 = monotonic()
                 stamps = None
                 if self.rank == 0:
                     self.bookkeep_raw(allraw)
-                    _t3 = _tm.monotonic()
+                    t3 = monotonic()
                     game_idx += len(allraw["n_plies"])
                     if own_files:
                         stamps = self._next_block_stamps(per_rank)
-                        block_game_idx.append(game_idx)
-                    elif stream:
-                        writer.submit(rest, local_idx + shipped, game_idx)   # (the index file moves once the block's last file is written)
-                        del rest
-                    elif writer is not None:
-                        writer.submit(allraw, local_idx, game_idx)
-                    else:
-                        self.write_raw(allraw, local_idx)
-                        self._write_game_idx(game_idx)
+                        files.block_game_idx.append(game_idx)
+                    else:   # (the index file moves once the block's last file is written)
+                        files.write(mine, local_idx + first_row, game_idx)
                     # where a block's wall time went on this rank (bench.py worker_end_to_end_config1): playing, the gather + the
                     # records' copy to the host, the resignation bookkeeping, waiting for the writer to take the block
-                    acc = self.run_seconds = getattr(self, "run_seconds", None) or {"play": 0.0, "gather_and_copy": 0.0, "bookkeeping": 0.0, "handing_to_the_writer": 0.0}
-                    for k_, v_ in (("play", _t1 - _t0), ("gather_and_copy", _t2 - _t1), ("bookkeeping", _t3 - _t2), ("handing_to_the_writer", _tm.monotonic() - _t3)):
-                        acc[k_] += v_
+                    for k, v in (("play", t1 - t0), ("gather_and_copy", t2 - t1), ("bookkeeping", t3 - t2), ("handing_to_the_writer", monotonic() - t3)):
+                        self.run_seconds[k] += v
                 if self._group():
                     t = [game_idx, self.config.play.resign_threshold, stamps]
                     dist.broadcast_object_list(t, src=0)
                     game_idx, self.config.play.resign_threshold, stamps = t
                 if own_files:
-                    first_local = local_idx + self.rank * per_rank
-                    base = stamps + timedelta(microseconds=self.rank * (per_rank + 8))
-                    if writer is not None:
-                        writer.submit(mine, first_local, None, quiet=True, stamp_base=base)
-                    elif inline["error"] is None:
-                        try:
-                            self.write_raw(mine, first_local, stamp_base=base)
-                            inline["written"] += 1
-                        except Exception as ex:   # noqa: BLE001 - agreed on by all ranks in the next block state
-                            inline["error"] = RuntimeError(f"writing play data failed: {ex!r}")
-                    del mine
+                    files.write(mine, local_idx + first_row, None, stamp_base=stamps + timedelta(microseconds=self.rank * (per_rank + 8)))
+                del allraw, mine
                 local_idx += per_rank * self.world
                 if reload_model is not None:
                     blob = reload_model() if self.rank == 0 else None   # rank 0 decides; the digest of ITS read is what counts
@@ -1030,17 +976,54 @@ class BatchedSelfPlayWorker:
                         self.set_net_blob(blob)
             finished = True
         finally:
-            _sys.setswitchinterval(_switch)
-            if writer is not None:
-                try:
-                    writer.close(quiet=own_files)
-                finally:
-                    self.last_writer_busy_seconds, self.last_writer_batches = writer.busy_seconds, writer.batches
+            sys.setswitchinterval(switch)
+            files.close()
         if own_files and finished:
             # every rank's writer is closed: agree that all files are on disk (or fail together), then rank 0 finishes the run
-            agree(self.BLOCK_OK)
+            files.agree(self.BLOCK_OK)
             if self.rank == 0:
                 self.remove_play_data()
+
+    def _deadline_passed(self, until):
+        """run(until=...): whether the time.monotonic() deadline has passed - on rank 0's clock, for all ranks."""
+        import time
+        stop = [time.monotonic() >= until]
+        if self._group():
+            import torch.distributed as dist
+            dist.broadcast_object_list(stop, src=0)
+        return stop[0]
+
+    def _summaries_to_rank0(self, summary):
+        """gather_summaries under this worker's process group, the transfer noted in last_gather_*."""
+        import torch.distributed as dist
+        allraw, self.last_gather_bytes = gather_summaries(summary, self.rank, self.world)
+        self.last_gather_backend = dist.get_backend()
+        return allraw
+
+    def _collect_block(self, block, own_files, streamed):
+        """A played Block from HBM to where it is needed.  Returns (what rank 0 bookkeeps - None on the other ranks -, the records this
+        rank writes - None if it writes nothing -, the block row these start at: local game index = the block's first + that row).
+        Per-rank emission: this rank's own records, cut to ITS longest game (nothing has to agree in shape but the summaries), and
+        every rank's 32-byte summaries for rank 0.  Streamed emission (one rank): the rest of the block - what was not shipped while
+        it was played - and every game's summary (under a process group of one rank these take the collective's path).  Otherwise
+        rank 0 gets and writes every rank's records (gather_packed, the path's single collective); one rank on its own just copies."""
+        from ..engine import bookkeeping_from_summaries, packed_to_host
+        if own_files:
+            pk = block()
+            mine = packed_to_host(pk)
+            return self._summaries_to_rank0(pk["summary"]), mine, self.rank * block.ids
+        if streamed:
+            shipped = self._streamed_rows
+            rest = block.to_host(None, shipped)
+            summary = block(1)["summary"]
+            return (self._summaries_to_rank0(summary) if self._group() else bookkeeping_from_summaries(summary.cpu().numpy())), rest, shipped
+        if self._group():
+            import torch.distributed as dist
+            allraw, self.last_gather_bytes = gather_packed(block, self.rank, self.world)
+            self.last_gather_backend = dist.get_backend()
+        else:
+            allraw = block.to_host()
+        return allraw, allraw, 0
 
     def _write_game_idx(self, game_idx):
         with open(self.config.resource.self_play_game_idx_file, "wt") as f:
@@ -1053,6 +1036,63 @@ class BatchedSelfPlayWorker:
         self.net_blob = blob
         self._f32_fallback = False
         self._drop_engine(net_too=True)
+
+
+class _BlockFiles:
+    """What one run() keeps about the files of its blocks: who writes them - a _BackgroundWriter, or the play loop itself -, how many
+    blocks this rank has on disk, and - rank 0, per-rank emission (own_files) - how far data/.self-play-game-idx may advance."""
+
+    def __init__(self, worker, own_files, background, depth=1):
+        self.worker, self.own_files = worker, own_files
+        self.writer = _BackgroundWriter(worker, depth=depth) if (background and (worker.rank == 0 or own_files)) else None
+        self.inline_written, self.inline_error = 0, None   # per-rank emission without the background thread
+        self.block_game_idx = []   # rank 0, per-rank emission: the game index after each block ...
+        self.idx_blocks = 0        # ... and the number of blocks the game index file has been advanced past
+
+    def agree(self, state):
+        """The block state all ranks share (raises on every rank if one of them failed) - and, failed or not, the game index
+        file advanced to the last block the same collective showed on disk everywhere.  Per-rank emission: a rank whose writer has
+        failed says so in the block state, so that every rank stops with it (raised on that rank alone, the others would wait for
+        it in the next collective)."""
+        w = self.worker
+        if self.own_files and state != w.BLOCK_FATAL:
+            err = self.inline_error if self.writer is None else (self.writer.take_error() if self.writer.failed else None)
+            if err is not None:
+                w._block_error, state = err, w.BLOCK_FATAL
+        try:   # (with the number of blocks whose files THIS rank has on disk)
+            return w._all_ranks_state(state, self.writer.batches if self.writer is not None else self.inline_written)
+        finally:
+            done = min(w._blocks_written_everywhere, len(self.block_game_idx))
+            if w.rank == 0 and self.own_files and done > self.idx_blocks:
+                self.idx_blocks = done
+                w._write_game_idx(self.block_game_idx[done - 1])
+
+    def write(self, raw, local_idx, game_idx, stamp_base=None):
+        """Hand finished games to the writer thread, or write them here.  game_idx: what data/.self-play-game-idx becomes once they
+        are written.  Per-rank emission (game_idx None: rank 0 moves the index once EVERY rank has written the block; file names from
+        stamp_base): a failure is not raised on this rank alone but kept for the next block state (agree)."""
+        if not self.own_files:
+            if self.writer is not None:
+                self.writer.submit(raw, local_idx, game_idx)
+            else:
+                self.worker.write_raw(raw, local_idx)
+                self.worker._write_game_idx(game_idx)
+        elif self.writer is not None:
+            self.writer.submit(raw, local_idx, None, quiet=True, stamp_base=stamp_base)
+        elif self.inline_error is None:
+            try:
+                self.worker.write_raw(raw, local_idx, stamp_base=stamp_base)
+                self.inline_written += 1
+            except Exception as ex:   # noqa: BLE001 - agreed on by all ranks in the next block state
+                self.inline_error = RuntimeError(f"writing play data failed: {ex!r}")
+
+    def close(self):
+        """Wait for the writer to finish (raising what it failed with, unless the ranks agree on that afterwards)."""
+        if self.writer is not None:
+            try:
+                self.writer.close(quiet=self.own_files)
+            finally:
+                self.worker.last_writer_busy_seconds, self.worker.last_writer_batches = self.writer.busy_seconds, self.writer.batches
 
 
 class _BackgroundWriter:
@@ -1126,89 +1166,6 @@ class _BackgroundWriter:
         self.thread.join()
         if not quiet:
             self._check(closing=True)
-
-
-# ---- the single collective: finished-game records -> rank 0 ------------------------------------------
-def pack_records(records):
-    """Fixed-layout numpy packing of [(plies, summary)] for the gather: per game a 64-byte summary and
-    per ply 48 B header + 64 x u32 visit counts + 64 x f64 saved policy."""
-    n = len(records)
-    maxp = max((len(p) for p, _ in records), default=0)
-    summ = np.zeros((n, 8), dtype=np.int64)
-    hdr = np.zeros((n, maxp, 6), dtype=np.float64)   # player turn action has_row n q  (+ own/enemy below)
-    boards = np.zeros((n, maxp, 2), dtype=np.uint64)
-    sims = np.zeros((n, maxp, 3), dtype=np.int64)
-    rootn = np.zeros((n, maxp, 64), dtype=np.float64)
-    pol = np.zeros((n, maxp, 64), dtype=np.float64)
-    for i, (plies, s) in enumerate(records):
-        summ[i] = [s["winner"], s["status"], len(plies), s["game_id"], s["enable_resign"], s["resigned_black"],
-                   s["resigned_white"], 0]
-        boards_final = (s["black"], s["white"])
-        for j, p in enumerate(plies):
-            hdr[i, j] = [p["player"], p["turn"], p["action"], int(p["has_row"]), p["n"], p["q"]]
-            boards[i, j] = [p["own"], p["enemy"]]
-            sims[i, j] = [p["sims"], p["loops"], int(bool(p.get("solved", False)))]
-            rootn[i, j] = p["root_n"]
-            pol[i, j] = p["saved_policy"]
-        summ[i, 7] = 0
-    finals = np.array([[s["black"], s["white"]] for _, s in records], dtype=np.uint64).reshape(n, 2)
-    return {"summ": summ, "hdr": hdr, "boards": boards, "sims": sims, "rootn": rootn, "pol": pol, "finals": finals}
-
-
-def unpack_records(pk):
-    out = []
-    for i in range(pk["summ"].shape[0]):
-        w, status, npl, gid, er, rb, rw, _ = (int(v) for v in pk["summ"][i])
-        plies = []
-        for j in range(npl):
-            pl, turn, act, hr, n, q = pk["hdr"][i, j]
-            plies.append({"player": int(pl), "turn": int(turn), "own": int(pk["boards"][i, j, 0]),
-                          "enemy": int(pk["boards"][i, j, 1]), "action": int(act), "has_row": bool(hr),
-                          "sims": int(pk["sims"][i, j, 0]), "loops": int(pk["sims"][i, j, 1]),
-                          "solved": bool(pk["sims"][i, j, 2]), "n": float(n),
-                          "q": float(q), "root_n": [float(v) for v in pk["rootn"][i, j]], "root_w": None,
-                          "saved_policy": [float(v) for v in pk["pol"][i, j]]})
-        out.append((plies, {"winner": w, "status": status, "plies": npl, "game_id": gid, "enable_resign": er,
-                            "resigned_black": rb, "resigned_white": rw, "black": int(pk["finals"][i, 0]),
-                            "white": int(pk["finals"][i, 1])}))
-    return out
-
-
-def gather_records(records, rank, world, device=None):
-    """Gather every rank's finished-game records on rank 0 (returns [] elsewhere), ordered by rank,
-    i.e. by global game id.  One all_gather of sizes + one gather per packed array — the only
-    communication in the whole self-play path."""
-    import torch
-    import torch.distributed as dist
-    pk = pack_records(records)
-    backend = dist.get_backend()
-    dev = torch.device(device) if device is not None else (
-        torch.device("cuda", torch.cuda.current_device()) if backend == "nccl" else torch.device("cpu"))
-    shape = torch.tensor([pk["summ"].shape[0], pk["hdr"].shape[1]], dtype=torch.int64, device=dev)
-    shapes = [torch.zeros_like(shape) for _ in range(world)]
-    dist.all_gather(shapes, shape)
-    max_n = int(max(s[0] for s in shapes))
-    max_p = int(max(s[1] for s in shapes))
-    gathered = {}
-    for k in ("summ", "hdr", "boards", "sims", "rootn", "pol", "finals"):
-        a = pk[k]
-        pad_shape = (max_n,) + ((max_p,) + a.shape[2:] if a.ndim >= 3 else a.shape[1:])
-        buf = np.zeros(pad_shape, dtype=a.dtype)
-        buf[tuple(slice(0, s) for s in a.shape)] = a
-        view = buf.view(np.int64) if buf.dtype == np.uint64 else buf
-        t = torch.from_numpy(view).to(dev)
-        lst = [torch.empty_like(t) for _ in range(world)] if rank == 0 else None
-        dist.gather(t, lst, dst=0)
-        if rank == 0:
-            gathered[k] = [x.cpu().numpy().view(a.dtype) for x in lst]
-    if rank != 0:
-        return []
-    out = []
-    for r in range(world):
-        n_r, p_r = int(shapes[r][0]), int(shapes[r][1])
-        part = {k: gathered[k][r][:n_r] for k in gathered}
-        out += unpack_records(part)
-    return out
 
 
 def load_model(config):

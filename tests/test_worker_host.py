@@ -116,68 +116,6 @@ def test_host_rng_matches_oracle():
         assert rng_pair(*args) == O.rng_pair(*args)
 
 
-def test_pack_unpack_roundtrip():
-    from reversi_alpha_zero_amd.worker.self_play import pack_records, unpack_records
-    recs = _fake_records(0, 5)
-    back = unpack_records(pack_records(recs))
-    assert [[{k: v for k, v in p.items() if k != "root_w"} for p in pl] for pl, _ in back] == \
-           [[{k: v for k, v in p.items() if k != "root_w"} for p in pl] for pl, _ in recs]
-    assert [s for _, s in back] == [s for _, s in recs]
-
-
-def _fake_records(rank, n):
-    rng = np.random.default_rng(100 + rank)
-    out = []
-    for i in range(n):
-        npl = int(rng.integers(1, 9))
-        plies = []
-        for j in range(npl):
-            rn = [float(v) for v in rng.integers(0, 50, 64)]
-            plies.append({"player": 1 + j % 2, "turn": j, "own": int(rng.integers(0, 2**63)) * 2 + 1,
-                          "enemy": int(rng.integers(0, 2**63)), "action": int(rng.integers(-1, 64)),
-                          "has_row": bool(j % 3), "solved": bool(j % 5 == 4), "sims": 20, "loops": 1, "n": float(rng.integers(0, 9)),
-                          "q": float(rng.random()), "root_n": rn, "root_w": None,
-                          "saved_policy": [v / max(sum(rn), 1.0) for v in rn]})
-        out.append((plies, {"winner": int(rng.integers(1, 4)), "status": 1, "plies": npl, "game_id": rank * 1000 + i,
-                            "enable_resign": 1, "resigned_black": 0, "resigned_white": int(i % 2),
-                            "black": int(rng.integers(0, 2**63)) * 2 + 1, "white": int(rng.integers(0, 2**63))}))
-    return out
-
-
-_GATHER_SCRIPT = r'''
-import os, sys, json
-sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "tests"))
-import torch.distributed as dist
-from test_worker_host import _fake_records
-from reversi_alpha_zero_amd.worker.self_play import gather_records
-rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-dist.init_process_group("gloo", rank=rank, world_size=world)
-mine = _fake_records(rank, 3 + 2 * rank)          # ragged: ranks hold different numbers of games/plies
-got = gather_records(mine, rank, world)
-if rank == 0:
-    exp = _fake_records(0, 3) + _fake_records(1, 5)
-    strip = lambda recs: [[[{{k: v for k, v in p.items() if k != "root_w"}} for p in pl], s] for pl, s in recs]
-    assert strip(got) == strip(exp), "gathered records differ"
-    print("GATHER_OK", len(got))
-else:
-    assert got == []
-dist.barrier(); dist.destroy_process_group()
-'''
-
-
-def test_gather_records_two_ranks_gloo(tmp_path):
-    """The only collective of the path, at world_size 2 on CPU (gloo), ragged per-rank sizes."""
-    script = tmp_path / "gather2.py"
-    script.write_text(_GATHER_SCRIPT.format(root=ROOT))
-    _p = _free_port()
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=_p)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-                        "--master-addr", "127.0.0.1", "--master-port", _p, str(script)],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "GATHER_OK 8" in r.stdout
-
-
 def test_convert_to_training_data_equals_reference_recipe():
     """lib/data_helper.convert_to_training_data == the reference's per-row bit_to_array recipe
     (worker/optimize.py:214-231) on golden rows, including boards with bit 63 set."""
@@ -343,40 +281,6 @@ def test_emit_raw_writes_the_same_files_as_emit(tmp_path):
         p_py, g_py, book_py, _ = run("py", tau1)
         p_raw, g_raw, book_raw, _ = run("raw", tau1)
         assert len(p_py) >= 3 and p_py == p_raw and g_py == g_raw and book_py == book_raw
-
-
-_GATHER_RAW_SCRIPT = r'''
-import os, sys
-sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "tests")); sys.path.insert(0, os.path.join({root!r}, "oracle"))
-import numpy as np
-import torch.distributed as dist
-from test_worker_host import _fake_records, _raw_of_games
-from reversi_alpha_zero_amd.worker.self_play import gather_raw
-rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-dist.init_process_group("gloo", rank=rank, world_size=world)
-fix = lambda recs: [([dict(p, action=max(p["action"], 0)) for p in pl], s) for pl, s in recs]
-got = gather_raw(_raw_of_games(fix(_fake_records(rank, 4))), rank, world)
-if rank == 0:
-    exp = _raw_of_games(fix(_fake_records(0, 4) + _fake_records(1, 4)))
-    assert set(got) == set(exp) and all(np.array_equal(got[k], exp[k]) for k in exp), "gathered arrays differ"
-    print("GATHER_RAW_OK", len(got["n_plies"]))
-else:
-    assert got is None
-dist.barrier(); dist.destroy_process_group()
-'''
-
-
-def test_gather_raw_two_ranks_gloo(tmp_path):
-    """The collective of the worker's raw path at world_size 2 on CPU (gloo): rank-ordered concatenation."""
-    script = tmp_path / "gather_raw2.py"
-    script.write_text(_GATHER_RAW_SCRIPT.format(root=ROOT))
-    _p = _free_port()
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=_p)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-                        "--master-addr", "127.0.0.1", "--master-port", _p, str(script)],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "GATHER_RAW_OK 8" in r.stdout
 
 
 _GATHER_PACKED_SCRIPT = '''

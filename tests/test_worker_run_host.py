@@ -139,6 +139,29 @@ def test_run_background_writer_equals_inline(tmp_path):
     assert first == play[:len(first)] and len(first) >= 12
 
 
+def test_bookkeeping_from_summaries_equals_the_fields_of_raw_from_packed(tmp_path):
+    """The 32-byte summaries of a packed batch alone give what bookkeep_raw reads: the same arrays (values, shapes, element types)
+    raw_from_packed gives for the whole batch, which are the games' own facts; and the bookkeeping counts the same from either."""
+    from reversi_alpha_zero_amd.engine import bookkeeping_from_summaries, raw_from_packed
+    eng, n = make_stub_worker(make_config(tmp_path / "a"), games_in_flight=3).play_batch_raw(0)
+    pk = eng.pack_records(0, n)
+    raw = raw_from_packed(*(pk[k].numpy() for k in ("headers", "root_n", "summary")))
+    got = bookkeeping_from_summaries(pk["summary"].numpy())
+    assert sorted(got) == ["enable_resign", "game_id", "n_plies", "resigned", "status"]
+    for k, v in got.items():
+        assert v.dtype == raw[k].dtype and v.shape == raw[k].shape and np.array_equal(v, raw[k]), k
+    games = stub_games(0, 3)
+    assert got["game_id"].tolist() == [0, 1, 2] and got["n_plies"].tolist() == [len(p) for p, _ in games]
+    assert got["status"].tolist() == [s["winner"] for _, s in games] and got["enable_resign"].tolist() == [s["enable_resign"] for _, s in games]
+    assert got["resigned"].tolist() == [[s["resigned_black"], s["resigned_white"]] for _, s in games]
+    counts = []
+    for tag, r in (("b", got), ("c", raw)):
+        w = make_stub_worker(make_config(tmp_path / tag), games_in_flight=3)
+        w.bookkeep_raw(r)
+        counts.append((w.resign_test_game_count, w.false_positive_count_of_resign))
+    assert counts[0] == counts[1] and counts[0][0] == 2   # (ids 0 and 2 are no-resign test games)
+
+
 def test_run_reports_writer_errors(tmp_path):
     """A failure in the background writer surfaces in run() (not silently lost), and the game index is not advanced past
     the batch whose files are missing - whatever the interleaving of the caller and the writer thread."""

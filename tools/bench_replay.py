@@ -90,11 +90,11 @@ def device_route(pk, cfg, reps):
 
 
 def file_route(player, pk, cfg, dev):
-    from reversi_alpha_zero_amd.engine import raw_from_packed
+    from reversi_alpha_zero_amd.engine import packed_to_host
     from reversi_alpha_zero_amd.lib.data_helper import get_game_data_filenames, pack_game_data, read_game_data_from_file
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    raw = raw_from_packed(*(pk[k].cpu().numpy() for k in ("headers", "root_n", "summary")))
+    raw = packed_to_host(pk)
     player.write_raw(raw, 1)
     t1 = time.perf_counter()
     files = get_game_data_filenames(cfg.resource)

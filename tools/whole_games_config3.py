@@ -35,7 +35,7 @@ def main():
     import bench
     import oracle as O
     from reversi_alpha_zero_amd.agent.model import ReversiNet
-    from reversi_alpha_zero_amd.engine import DeviceNet, SelfPlayEngine, raw_from_packed
+    from reversi_alpha_zero_amd.engine import DeviceNet, SelfPlayEngine, packed_to_host
     dev = torch.device("cuda:0")
     cfg = bench.ch5_config(a.sims)
     blob = ReversiNet(256, 10, 256).keras_init_(0).to_blob()
@@ -55,7 +55,7 @@ def main():
     outbox, st = eng.play_continuous(0, a.games, lambda gid: a.sims, chunk=256, on_chunk=progress)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    raw = raw_from_packed(*(outbox[k].cpu().numpy() for k in ("headers", "root_n", "summary")))
+    raw = packed_to_host(outbox)
     searched = int((raw["headers"]["sims"] > 0).sum())
     out = {"workload": f"{a.games} complete self-play games on {a.slots} slots (continuous batching), 256x10 net (split-f16 trunk), {a.sims} sims/move, "
                        "ch5.yml play settings, thinking_loop=1, solver off, parallel_search_num=1, node pools 16 x sims (k_gc between harvests)",
