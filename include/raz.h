@@ -639,6 +639,65 @@ int raz_train_rows_fill(const void* d_headers, const uint32_t* d_root_n, const r
                         const uint32_t* d_row_offset, uint64_t capacity_rows, uint64_t* d_own, uint64_t* d_enemy, float* d_policy,
                         int8_t* d_z, raz_stream_t stream);
 
+/* ---- evaluation matches on the device: the hand-off between two engines (csrc/raz_match.h) -----------------------
+ * The reference's evaluator (worker/evaluate.py:66-96) plays best model against challenger with two ReversiPlayer objects and one
+ * ReversiEnv per game.  A match couples two STARTED engines of the same n_games - slot g of each is that model's player in game g,
+ * with the tree, random streams and one-move semantics raz_engine_set_position gives it - and keeps every game's env in a
+ * caller-provided device workspace (raz_match_workspace_bytes(n_games) bytes, 256-byte aligned, owned by the caller, as are the
+ * engines, for the lifetime of the handle; 0 is returned for n_games == 0):
+ *   raz_match_stats u32[8] | raz_match_game [n_games] | raz_match_ply [n_games][64] | root visit counts u32 [n_games][64][64],
+ *   each section rounded up to 256 bytes.
+ * raz_match_start: game g is (d_black[g], d_white[g], d_player[g] 1 black / 2 white to move) - the three arrays are nullable, all or
+ *   none: NULL = the initial position, black to move; the caller guarantees playable positions, as with raz_engine_set_positions -
+ *   and the best model plays black where d_best_is_black[g] != 0.  One launch clears the log and arms the side to move of every game
+ *   in its model's engine: the mover's own discs as "black", player 1, sims_best / sims_challenger simulations, one move.
+ * raz_match_turn: one launch over all games.  A live game whose searching slot has decided (phase idle, one ply recorded) gets the
+ *   ply appended to its log (who, action, turn, the 64 root visit counts), its board and status translated from the mover's frame to
+ *   absolute colours, and either its outcome stored or the next mover's slot armed - the other engine's, or the same one again when
+ *   the opponent had to pass.  A game whose slot is still searching is left alone.  A slot that carries an engine error flag, or that
+ *   left the one-move protocol, ends its game and marks `error` (the engine's flags; RAZ_MATCH_ERR_SLOT / _LOG_FULL): a match never
+ *   spins.
+ * raz_match_stats_sync: the counters (synchronises `stream`).  raz_match_read: the games and, optionally, the log, to host arrays of
+ *   n_games, n_games x 64 and n_games x 64 x 64 entries (any may be NULL; synchronises `stream`).
+ * RAZ_EINVAL / RAZ_ESTATE with a message and NO launch: a NULL argument, engines of different n_games or not started, a workspace that
+ *   is NULL, misaligned or short, sims of 0, position arrays given in part, turn / read before start. */
+typedef struct raz_match raz_match;
+typedef struct {
+    uint64_t black, white;       /* the real board, absolute colours */
+    uint8_t player;              /* side to move: 1 black / 2 white */
+    uint8_t best_is_black;
+    uint8_t searching;           /* whose slot is searching: 0 nobody (the game has ended), 1 the best model's, 2 the challenger's */
+    uint8_t winner;              /* 0 running; 1 black / 2 white / 3 draw */
+    uint8_t blacks, whites;      /* disc counts when the game ended */
+    uint8_t n_plies;             /* entries of the game's log */
+    uint8_t flags;               /* 0x10 ended by an illegal move, 0x20 by a resignation (as raz_env_step) */
+    uint32_t pad[2];
+} raz_match_game;                /* 32 bytes */
+typedef struct {
+    uint8_t who;                 /* 0 the best model moved, 1 the challenger */
+    int8_t action;               /* 0..63, -1 = resigned */
+    uint8_t turn, pad;
+} raz_match_ply;                 /* 4 bytes */
+typedef struct {
+    uint32_t live;               /* games still running */
+    uint32_t searching_best, searching_challenger;   /* slots searching per side */
+    uint32_t plies;              /* plies handed off since raz_match_start */
+    uint32_t error;              /* 0, or engine error flags of a slot (1 pool, 2 table, 4 records, 8 path) | RAZ_MATCH_ERR_* */
+    uint32_t pad[3];
+} raz_match_stats;               /* 32 bytes */
+#define RAZ_MATCH_ERR_SLOT 0x100u       /* a searching slot finished outside the one-move protocol (phase done, or idle without exactly one ply) */
+#define RAZ_MATCH_ERR_LOG_FULL 0x200u   /* a game's 65th ply */
+#define RAZ_MATCH_MAX_PLIES 64
+size_t raz_match_workspace_bytes(uint32_t n_games);
+int raz_match_create(raz_engine* best_engine, raz_engine* challenger_engine, void* d_workspace, size_t workspace_bytes,
+                     raz_match** out);
+void raz_match_destroy(raz_match* m);
+int raz_match_start(raz_match* m, const uint8_t* d_best_is_black, const uint64_t* d_black, const uint64_t* d_white,
+                    const uint8_t* d_player, uint32_t sims_best, uint32_t sims_challenger, int enable_resign, raz_stream_t stream);
+int raz_match_turn(raz_match* m, raz_stream_t stream);
+int raz_match_stats_sync(raz_match* m, raz_match_stats* out, raz_stream_t stream);
+int raz_match_read(raz_match* m, raz_match_game* games, raz_match_ply* log, uint32_t* log_root_n, raz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,11 @@ class RazEngineStats(ctypes.Structure):
                 ("max_pool_bytes", c_uint64)]
 
 
+class RazMatchStats(ctypes.Structure):
+    _fields_ = [("live", c_uint32), ("searching_best", c_uint32), ("searching_challenger", c_uint32), ("plies", c_uint32),
+                ("error", c_uint32), ("pad", c_uint32 * 3)]
+
+
 SIGNATURES.update({
     "raz_net_weight_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raz_net_scratch_bytes": (c_size_t, [c_int, c_int, c_size_t]),
@@ -158,6 +163,14 @@ SIGNATURES.update({
     "raz_train_rows_count": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, POINTER(c_uint64), c_void_p]),
     "raz_train_rows_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_int, c_void_p, c_uint64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # evaluation matches on the device (csrc/raz_match.h); the match handle travels as c_void_p
+    "raz_match_workspace_bytes": (c_size_t, [c_uint32]),
+    "raz_match_create": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_void_p)]),
+    "raz_match_destroy": (None, [c_void_p]),
+    "raz_match_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_int, c_void_p]),
+    "raz_match_turn": (c_int, [c_void_p, c_void_p]),
+    "raz_match_stats_sync": (c_int, [c_void_p, POINTER(RazMatchStats), c_void_p]),
+    "raz_match_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

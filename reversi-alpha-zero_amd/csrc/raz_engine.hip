@@ -907,9 +907,11 @@ extern "C" int raz_engine_stats_sync(raz_engine* e, raz_engine_stats* out, raz_s
 }
 
 namespace {
-__global__ void k_set_position(raz_engine_dev E, uint32_t g, unsigned long long black, unsigned long long white,
-                               uint32_t player, uint32_t sims, uint32_t enable_resign, uint32_t one_move) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// Arming a slot, stated once: put slot g on (black, white, `player` to move) and ask for a move of `sims` simulations, keeping the
+// slot's tree, random-stream counters and - unless one_move - its records.  One thread per slot; called by k_set_position,
+// k_set_positions and the match kernels (raz_match.h).
+__device__ __forceinline__ void arm_slot(const raz_engine_dev& E, uint32_t g, unsigned long long black, unsigned long long white,
+                                         uint32_t player, uint32_t sims, uint32_t enable_resign, uint32_t one_move) {
     raz_game& G = E.game[g];
     G.root_black = black;
     G.root_white = white;
@@ -929,30 +931,19 @@ __global__ void k_set_position(raz_engine_dev E, uint32_t g, unsigned long long 
     if (one_move) G.n_plies = 0;  // the facade reads each ply back right after it is decided
 }
 
+__global__ void k_set_position(raz_engine_dev E, uint32_t g, unsigned long long black, unsigned long long white,
+                               uint32_t player, uint32_t sims, uint32_t enable_resign, uint32_t one_move) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    arm_slot(E, g, black, white, player, sims, enable_resign, one_move);
+}
+
 // The same for slots first_slot .. first_slot + n - 1 at once, positions in device arrays (one thread per slot).
 __global__ void k_set_positions(raz_engine_dev E, uint32_t first_slot, uint32_t n, const unsigned long long* black,
                                 const unsigned long long* white, const uint8_t* player, uint32_t sims, uint32_t enable_resign,
                                 uint32_t one_move) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t g = first_slot + i;
-    raz_game& G = E.game[g];
-    G.root_black = black[i];
-    G.root_white = white[i];
-    G.player = player[i];
-    G.status = 0;
-    G.phase = RAZ_PHASE_NEW_MOVE;
-    G.sims_per_move = sims;
-    G.sims_left = 0;
-    G.loops_done = 0;
-    G.move_sims = 0;
-    G.leaf_kind = RAZ_LEAF_NONE;
-    if (!E.par) E.nn_active[g] = 0;
-    G.par_stage = 0;
-    G.enable_resign = enable_resign;
-    G.one_move = one_move;
-    G.root_node = RAZ_NO_NODE;
-    if (one_move) G.n_plies = 0;
+    arm_slot(E, first_slot + i, black[i], white[i], player[i], sims, enable_resign, one_move);
 }
 
 // var_n[key] / var_w[key] / var_p[key] of one slot: copy the node of (black, white, next_player)
@@ -1076,6 +1067,8 @@ extern "C" int raz_engine_set_positions(raz_engine* e, uint32_t first_slot, uint
                        (uint32_t)(enable_resign != 0), (uint32_t)(one_move != 0));
     return raz_check_launch("raz_engine_set_positions");
 }
+
+#include "raz_match.h"   // evaluation matches on the device: the hand-off between two engines (raz_match_*)
 
 // Prune unreachable nodes (positions with fewer discs than the current real position) in every
 // game whose pool holds at least `threshold` nodes.  Asynchronous on `stream`; call between

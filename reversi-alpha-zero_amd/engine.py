@@ -1,5 +1,5 @@
-"""Host-side driver objects over the C ABI (include/raz.h): DeviceNet (raz_net_*) and
-SelfPlayEngine (raz_engine_*).  torch is used only to own HBM buffers and the HIP stream.
+"""Host-side driver objects over the C ABI (include/raz.h): DeviceNet (raz_net_*),
+SelfPlayEngine (raz_engine_*) and DeviceMatch (raz_match_*).  torch is used only to own HBM buffers and the HIP stream.
 
 SelfPlayEngine replaces, for a batch of concurrent games, the reference's
 SelfPlayWorker.start_game loop (worker/self_play.py:139-175) with two ReversiPlayers per game
@@ -610,6 +610,121 @@ class SelfPlayEngine:
                                 "resigned_black": int(raw["resigned"][g, 0]), "resigned_white": int(raw["resigned"][g, 1]),
                                 "black": int(raw["final_black"][g]), "white": int(raw["final_white"][g])}))
         return out
+
+
+MATCH_GAME = np.dtype([("black", "<u8"), ("white", "<u8"), ("player", "u1"), ("best_is_black", "u1"), ("searching", "u1"),
+                       ("winner", "u1"), ("blacks", "u1"), ("whites", "u1"), ("n_plies", "u1"), ("flags", "u1"), ("pad", "<u4", (2,))])
+MATCH_PLY = np.dtype([("who", "u1"), ("action", "i1"), ("turn", "u1"), ("pad", "u1")])
+assert MATCH_GAME.itemsize == 32 and MATCH_PLY.itemsize == 4
+MATCH_MAX_PLIES = 64   # include/raz.h RAZ_MATCH_MAX_PLIES
+
+
+def match_error_text(error):
+    return (f"match error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
+            f"0x100 a slot left the one-move protocol, 0x200 a game's log is full): the games it hit ended undecided")
+
+
+def match_results(games):
+    """Per game (ng_win: 1 / 0 / None for a draw, best_is_black, (blacks, whites)) - what EvaluateWorker.play_games returns - from the
+    MATCH_GAME records of a finished match."""
+    out = []
+    for r in games:
+        w, bib = int(r["winner"]), bool(r["best_is_black"])
+        out.append((int((w == 1) != bib) if w in (1, 2) else None, bib, (int(r["blacks"]), int(r["whites"]))))
+    return out
+
+
+def match_games(games, log, log_n, first_game_id=0):
+    """The match ply by ply, in the dictionaries of EvaluateWorker.last_games, from raz_match_read's host arrays."""
+    log, log_n = log.reshape(len(games), MATCH_MAX_PLIES), log_n.reshape(len(games), MATCH_MAX_PLIES, 64)
+    return [{"game_id": first_game_id + g, "best_is_black": bool(r["best_is_black"]),
+             "plies": [{"who": "ng" if log[g, i]["who"] else "best", "action": int(log[g, i]["action"]), "root_n": log_n[g, i].copy()}
+                       for i in range(int(r["n_plies"]))]} for g, r in enumerate(games)]
+
+
+class DeviceMatch:
+    """A match of two started engines of the same n_games on the device (include/raz.h raz_match_*): slot g of `best_engine` is the
+    best model's player in game g, slot g of `challenger_engine` the challenger's.  The caller steps the engines; turn() hands every
+    decided move to the other side's slot where it lies, without a host round trip."""
+
+    def __init__(self, best_engine, challenger_engine, workspace=None):
+        """workspace: a uint8 device tensor of at least workspace_bytes + 255 bytes to keep the match in (None: the match's own)."""
+        import torch
+        if best_engine.n_games != challenger_engine.n_games:
+            raise ValueError("the two engines of a match need the same n_games")
+        self.best, self.challenger = best_engine, challenger_engine
+        self.device, self.n_games = best_engine.device, best_engine.n_games
+        self.workspace_bytes = lib.raz_match_workspace_bytes(self.n_games)
+        if workspace is None:
+            workspace = torch.zeros(self.workspace_bytes + 256, dtype=torch.uint8, device=self.device)
+        self._ws = workspace
+        base = self.workspace_base = (workspace.data_ptr() + 255) // 256 * 256
+        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+                and base + self.workspace_bytes <= workspace.data_ptr() + workspace.numel()):
+            raise ValueError("workspace: a contiguous uint8 device tensor with workspace_bytes behind its first 256-byte boundary")
+        self._h = ctypes.c_void_p()
+        check(lib.raz_match_create(best_engine._h, challenger_engine._h, base, self.workspace_bytes, ctypes.byref(self._h)), "raz_match_create")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib.raz_match_destroy(h)
+            self._h = None
+
+    def start(self, best_is_black, positions=None, sims_best=None, sims_challenger=None, enable_resign=True):
+        """best_is_black: uint8 / bool device tensor [n_games].  positions: None (the initial position, black to move) or
+        (black int64, white int64, player uint8) device tensors [n_games], playable positions.  sims_*: simulations a move."""
+        import torch
+        tensors = [best_is_black] + list(positions or ())
+        if positions is not None and len(positions) != 3:
+            raise ValueError("positions is (black, white, player)")
+        for t in tensors:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == self.n_games):
+                raise ValueError("DeviceMatch.start takes contiguous device tensors of n_games entries (no CPU tensors)")
+        if best_is_black.dtype not in (torch.uint8, torch.bool) or (positions is not None and (
+                positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8)):
+            raise ValueError("best_is_black: uint8 / bool; positions: int64, int64, uint8")
+        if not sims_best:
+            raise ValueError("sims_best: simulations a move")
+        self._args = tensors   # (kept alive until the launch has run)
+        b, w, p = (t.data_ptr() for t in positions) if positions is not None else (None, None, None)
+        with torch.cuda.device(self.device):
+            check(lib.raz_match_start(self._h, best_is_black.data_ptr(), b, w, p, int(sims_best), int(sims_challenger or sims_best),
+                                      int(enable_resign), _stream()), "raz_match_start")
+
+    def turn(self):
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib.raz_match_turn(self._h, _stream()), "raz_match_turn")
+
+    def stats(self, raise_on_error=True):
+        """{"live", "searching_best", "searching_challenger", "plies", "error"}; raises on the match's error word.  Synchronises."""
+        import torch
+        st = N.RazMatchStats()
+        with torch.cuda.device(self.device):
+            check(lib.raz_match_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_match_stats_sync")
+        if st.error and raise_on_error:
+            raise RuntimeError(match_error_text(st.error))
+        return {"live": st.live, "searching_best": st.searching_best, "searching_challenger": st.searching_challenger, "plies": st.plies,
+                "error": st.error}
+
+    def read(self, log=True):
+        """(MATCH_GAME [n], MATCH_PLY [n, 64] or None, root visit counts i32 [n, 64, 64] or None) on the host."""
+        import torch
+        n = self.n_games
+        games = np.zeros(n, dtype=MATCH_GAME)
+        plies = np.zeros((n, MATCH_MAX_PLIES), dtype=MATCH_PLY) if log else None
+        root_n = np.zeros((n, MATCH_MAX_PLIES, 64), dtype=np.int32) if log else None
+        with torch.cuda.device(self.device):
+            check(lib.raz_match_read(self._h, games.ctypes.data, plies.ctypes.data if log else None, root_n.ctypes.data if log else None,
+                                     _stream()), "raz_match_read")
+        return games, plies, root_n
+
+    def results(self):
+        return match_results(self.read(log=False)[0])
+
+    def games(self, first_game_id=0):
+        return match_games(*self.read(), first_game_id=first_game_id)
 
 
 GAME_SUMMARY = np.dtype([("final_black", "<u8"), ("final_white", "<u8"), ("game_id", "<u4"), ("n_plies", "<u4"),

@@ -32,9 +32,17 @@ from ..lib.model_helpler import load_best_model_weight, save_as_best_model
 logger = getLogger(__name__)
 
 
-def start(config, max_models=None, seed=0):
-    """evaluate.py:17-19.  max_models: stop after that many challengers (None = keep polling, as the reference)."""
-    return EvaluateWorker(config, seed=seed).start(max_models=max_models)
+# handoff="device": engine steps between two hand-offs (raz_match_turn), and hand-offs between two reads of the counters.  Their
+# product is the horizon of _Side.busy's pool check (64 steps, as the host route's step(64)); the split is README section 4.10's.
+STEPS_PER_TURN = 8
+TURNS_PER_STATS = 8
+
+
+def start(config, max_models=None, seed=0, handoff="host"):
+    """evaluate.py:17-19.  max_models: stop after that many challengers (None = keep polling, as the reference).
+    handoff: who hands a decided move to the other model's player - "host" (ReversiEnv objects, one round of all games at a time) or
+    "device" (engine.DeviceMatch: the games' boards stay in HBM and no game waits for another); the games are the same."""
+    return EvaluateWorker(config, seed=seed, handoff=handoff).start(max_models=max_models)
 
 
 def decide(outcomes, game_num, replace_rate):
@@ -94,7 +102,10 @@ class _Side:
 
 
 class EvaluateWorker:
-    def __init__(self, config, seed=0, device="cuda:0"):
+    def __init__(self, config, seed=0, device="cuda:0", handoff="host"):
+        if handoff not in ("host", "device"):
+            raise ValueError(f'handoff is "host" or "device", not {handoff!r}')
+        self.handoff = handoff
         self.config = config
         self.best_model = None
         self.seed = seed
@@ -135,6 +146,8 @@ class EvaluateWorker:
         best_is_black = [self.random.random() < 0.5 for _ in range(n)]
         sides = {True: _Side(self.config, best_model, n, 2 * self.seed, first, self.device),        # the best model
                  False: _Side(self.config, ng_model, n, 2 * self.seed + 1, first, self.device)}     # the challenger
+        if self.handoff == "device":
+            return self._play_on_device(sides, best_is_black, first)
         envs = [ReversiEnv().reset() for _ in range(n)]
         live = list(range(n))
         # what the match looked like, ply by ply (tests compare it with games of the reference's evaluate.py:66-96)
@@ -164,6 +177,32 @@ class EvaluateWorker:
                 ng_win = int((env.winner == Winner.black) != best_is_black[g])
             out.append((ng_win, best_is_black[g], env.observation.number_of_black_and_white))
         return out
+
+    def _play_on_device(self, sides, best_is_black, first):
+        """The match of play_games with the hand-off on the device (engine.DeviceMatch): no ReversiEnv, no raz_engine_set_position call
+        and no record copy per ply.  Both engines are stepped while either can have a searching slot; every TURNS_PER_STATS hand-offs
+        the counters are read once per object, which is also when each side's pool is checked and pruned."""
+        import torch
+        from ..engine import DeviceMatch, match_games, match_results
+        best, ng = sides[True], sides[False]
+        match = DeviceMatch(best.engine, ng.engine)
+        match.start(torch.tensor(best_is_black, dtype=torch.uint8, device=self.device), sims_best=best.sims, sims_challenger=ng.sims,
+                    enable_resign=True)
+        st = match.stats()   # raises on the match's error word
+        while st["live"]:
+            for i in range(TURNS_PER_STATS):
+                # (a hand-off may have armed a side that had no searching slot at the last read: only the first iteration knows)
+                if i or st["searching_best"]:
+                    best.engine.step(STEPS_PER_TURN)
+                if i or st["searching_challenger"]:
+                    ng.engine.step(STEPS_PER_TURN)
+                match.turn()
+            best.busy()
+            ng.busy()
+            st = match.stats()
+        games, plies, root_n = match.read()
+        self.last_games = match_games(games, plies, root_n, first_game_id=first)
+        return match_results(games)
 
     def play_game(self, best_model, ng_model):
         """evaluate.py:66-96: one game (a match of one)."""

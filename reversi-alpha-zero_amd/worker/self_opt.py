@@ -8,6 +8,10 @@ give - and OptimizeWorker(replay=...) trains one pass on the replay's window, sa
 does, so that the `eval` worker is unchanged.  The net that plays is the BEST model, reloaded by digest between blocks exactly as the
 `self` worker does it (try_reload_model).  With write_files=True the same games are also written as play_*.json (write_raw), for
 the reference's own consumers.  One rank: world > 1 is refused.
+
+evaluate=True closes the reference's third process into the loop as well: after a training pass every model under next_generation/
+is challenged in this process by EvaluateWorker(handoff="device") - the match whose hand-offs stay on the device - and promoted or
+removed as the `eval` worker does it, so that the next block's digest check finds a new best model without a second process.
 """
 import os
 from logging import getLogger
@@ -19,10 +23,47 @@ def _world():
     return int(os.environ.get("WORLD_SIZE", "1"))
 
 
-def start(config, games_in_flight=None, backend="hip", precision=None, write_files=False, total_blocks=None, seed=0, block_games=None):
+def evaluate_challengers(config, evaluator, player=None):
+    """Challenge every model under next_generation/ (evaluate.py:31-42 without the polling sleep: the directory is listed, never waited
+    for) with `evaluator`, an EvaluateWorker: the better one becomes the best model, every one is removed.  The two engines of a
+    challenge live for that challenge only; where they do not fit beside `player`'s self-play engine, that engine is dropped first
+    (BatchedSelfPlayWorker._drop_engine: the next block rebuilds it).  Returns [(model_dir, became_best)]."""
+    import gc
+    import torch
+    from ..lib.data_helper import get_next_generation_model_dirs
+    from ..lib.model_helpler import save_as_best_model
+    decisions = []
+    while get_next_generation_model_dirs(config.resource):
+        if evaluator.best_model is None:
+            evaluator.best_model = evaluator.load_best_model()
+        ng_model, model_dir = evaluator.load_next_generation_model()   # (a directory is there: it does not sleep)
+        draws = evaluator.random.getstate(), evaluator.games_played
+        try:
+            better = evaluator.evaluate_model(ng_model)
+        except torch.cuda.OutOfMemoryError:
+            if player is None or player._engine is None:
+                raise
+            logger.info("the evaluation engines do not fit beside the self-play engine: dropping it for the challenge")
+            player._drop_engine()
+            evaluator.random.setstate(draws[0])
+            evaluator.games_played = draws[1]
+            better = evaluator.evaluate_model(ng_model)
+        logger.info(f"evaluated {model_dir}: {'new best model' if better else 'best model kept'}")
+        if better:
+            save_as_best_model(ng_model)
+            evaluator.best_model = ng_model
+        evaluator.remove_model(model_dir)
+        decisions.append((model_dir, better))
+        gc.collect()
+        torch.cuda.empty_cache()   # the challenge's engines go back to the device before the next engine is sized
+    return decisions
+
+
+def start(config, games_in_flight=None, backend="hip", precision=None, write_files=False, total_blocks=None, seed=0, block_games=None,
+          evaluate=False):
     """Alternate play - store - train until total_blocks blocks have been played (None = forever).  Returns (the self-play worker, the
     optimize worker, the replay).  block_games: the game ids of a block (default: the `self` worker's default_block_games, rounded up to
-    whole play files)."""
+    whole play files).  evaluate: challenge the models a training pass saved, in this process (evaluate_challengers)."""
     if _world() > 1:
         raise ValueError(f"self_opt runs one process on one GPU (WORLD_SIZE={_world()}): run the `self` and `opt` workers for more")
     import torch
@@ -47,6 +88,7 @@ def start(config, games_in_flight=None, backend="hip", precision=None, write_fil
     trainer = OptimizeWorker(config, backend=backend, seed=seed, device=device, precision=precision, replay=replay)
     game_idx = read_as_int(rc.self_play_game_idx_file) or 0
     local_idx, blocks = 1, 0
+    evaluator = None
     while total_blocks is None or blocks < total_blocks:
         # ---- play
         # (a block during which the net left the f16 range of the split-operand trunk is void: played again on the exact-f32 kernels)
@@ -68,6 +110,11 @@ def start(config, games_in_flight=None, backend="hip", precision=None, write_fil
             trainer.training(max_epochs=1)
         else:
             logger.info(f"replay rows={replay.rows} is less than {config.trainer.min_data_size_to_learn}")
+        if evaluate:
+            if evaluator is None:
+                from .evaluate import EvaluateWorker
+                evaluator = EvaluateWorker(config, seed=seed, device=device, handoff="device")
+            evaluate_challengers(config, evaluator, player)
         new_blob = model.model.to_blob() if try_reload_model(config, model) else None
         if new_blob is not None:
             player.set_net_blob(new_blob)
