@@ -23,8 +23,25 @@
 //               half w & 1, the position group (w >> 1) & 1 (positions 0-3 or 4-7) and the row half w >> 2 (board rows 0-3 or 4-7);
 //               N tile j is board row 4 half + j, its column c is position c >> 3, file c & 7
 //   K loop    = 16 chunks x 3 tap groups (dy = -1, 0, +1) = 48 stages; a stage's weights (24 KB: 3 taps x 16 channels x 128 oc x
-//               {hi, lo}) and, once per chunk, the 8 positions' activations (32 KB) arrive by LDS-DMA in a double buffer while the
-//               previous stage's 3 taps x 8 tiles x 3 MFMAs per wave run: one barrier per stage, no register staging
+//               {hi, lo}) arrive by LDS-DMA TWO stages ahead in three buffers, and once per chunk the 8 positions' activations
+//               (32 KB) in two images, while the stages before them run 3 taps x 8 tiles x 3 MFMAs per wave: one barrier per stage,
+//               no register staging.  A stage has therefore been in LDS since the barrier BEFORE its own, and a wave reads each
+//               tap's operands while the tap before it computes - a stage's first tap during the last tap of the stage before,
+//               across the barrier (TapOps, tap_pipelined): after a barrier the matrix instructions start from registers
+//   hazards   = who writes each LDS area, who reads it last, and the barrier between (barrier s opens stage s = 3 c + tg; a wave drains
+//               its own DMA - the vmcnt(0) of __syncthreads - before it arrives at any barrier, so what was issued before barrier s - 1
+//               by anyone is in LDS when barrier s opens):
+//                 weight buffer tg   written: stage (c, tg)'s weights, issued after barrier s - 2 (stages 0 and 1: before barrier 0),
+//                                    so landed when barrier s - 1 opens.  Read: first tap during stage s - 1's last tap, after barrier
+//                                    s - 1; the rest in stage s.  Last read before barrier s + 1; next written (stage s + 3) after it.
+//                 image c & 1        written: chunk c's activations, issued after barrier 3 c - 2 (chunk 0: before barrier 0), landed
+//                                    when barrier 3 c - 1 opens.  Read: from the last tap of stage (c - 1, 2), after barrier 3 c - 1,
+//                                    to the end of stage (c, 2).  Last read before barrier 3 c + 3; next written (chunk c + 2) after
+//                                    barrier 3 c + 4.
+//                 zero areas         written once by threads 0..255 before barrier 0; only read afterwards.
+//                 after the last stage  the read-ahead reads buffer 0 and the other image once more: nothing is in flight into them
+//                                    and the values are not used.
+//                 skip rows (HBM)    a lane reads the 16 bytes it later overwrites itself, and no other lane or workgroup writes them.
 //   row skip  = with a tile being ONE board row, the taps dy = -1 of row 0 and dy = +1 of row 7 are whole all-zero B operands: a
 //               top-half wave issues neither reads nor matrix instructions for its tile 0 in the stages dy = -1, a bottom-half wave
 //               none for its tile 3 in the stages dy = +1 (6 of 72 tile-taps: 198 instead of 216 matrix instructions per wave and
@@ -72,9 +89,9 @@ constexpr int ACT_POS = 4 * 64 * 16;             // 4,096 B: [plane 4][square 64
 constexpr int Z_OFF = NWAVE * (ACT_POS + 128);   // the zero area inside an image, after the 8 positions (act_pos_off): 33,792
 constexpr int Z_BYTES = 2048;                    // a bank-class slot (< 256) + a row offset (<= 5 * 128) + the lo plane's 1,024 + 16 B
 constexpr int ACT_IMG = Z_OFF + Z_BYTES;         // one chunk's image: 8 positions + the zero area (35,840 B)
-constexpr int LDS_W = 0;                         // two weight stages (double buffer)
-constexpr int LDS_ACT = 2 * W_STAGE;             // two activation images (double buffer)
-constexpr int LDS_BYTES = LDS_ACT + 2 * ACT_IMG; // 120,832 B: one workgroup of 8 waves per CU
+constexpr int LDS_W = 0;                         // three weight stages (stage st lives in buffer st % 3 = its tap group)
+constexpr int LDS_ACT = 3 * W_STAGE;             // two activation images (chunk c lives in image c & 1)
+constexpr int LDS_BYTES = LDS_ACT + 2 * ACT_IMG; // 145,408 B: one workgroup of 8 waves per CU
 // Where position p (0..7) of the workgroup starts inside an image.  A B read takes 8 files x 4 positions; the LDS serves a 16-byte
 // read in the lane groups {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (and the same + 32), i.e. files 0-3 of positions 0 and 3 with
 // files 4-7 of positions 1 and 2, and the reverse.  With every position on the same 256-byte bank row those would meet two by two;
@@ -145,10 +162,87 @@ __device__ __forceinline__ void halves_trade(float a, float b, int upper, float&
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),                     \
                                      (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
-// One stage (tap group TG = dy + 1: three taps dx = -1, 0, +1) of a wave's tile: 2 output-channel tiles x the board rows J0 .. J1 - 1
-// of its row half.  Row j under tap dy reads board row 4 half + j + dy, which lies (j + TG) * 128 bytes above the row the three
-// per-lane addresses `boff` point at (4 half - 1).  Per accumulator the instructions come in the order they always had: tap
-// 0 .. 8, each al*bh, ah*bl, ah*bh.
+// The operands of ONE tap for the rows of a stage's main pass (up to 48 VGPRs; v3 half of that).  The main pass keeps two sets: the
+// matrix instructions of a tap run from one while the other is being read from LDS for the tap after it - for a stage's last tap
+// that is the FIRST tap (dx = -1) of the next stage, read before that stage's barrier.
+struct TapOps {
+    h8 bh[4], bl[4], ah[2], al[2];
+};
+
+// Read number k of a tap's operands, in the order the tap's matrix instructions first use them: al0, bh[J0], ah0, bl[J0], then
+// (bh, bl) of the rows after J0, then al1, ah1 (!SPLIT: ah0, the bh, ah1).  wtap = the tap's place in its weight buffer + the lane's
+// offset; btap = the lane's B address of that tap inside the image (abase + boff[tap]).
+template <bool SPLIT, int TG, int J0, int J1>
+__device__ __forceinline__ void tap_read(const unsigned char* lds, uint32_t wtap, uint32_t btap, int k, TapOps& p) {
+    constexpr int R = J1 - J0;
+    if constexpr (SPLIT) {
+        if (k == 0) p.al[0] = *(const h8*)(lds + wtap + 2048);
+        else if (k == 2) p.ah[0] = *(const h8*)(lds + wtap);
+        else if (k == 2 * R + 2) p.al[1] = *(const h8*)(lds + wtap + 512 + 2048);
+        else if (k == 2 * R + 3) p.ah[1] = *(const h8*)(lds + wtap + 512);
+        else {
+            const int b = k == 1 ? 0 : k == 3 ? 1 : k - 2;   // B read number: (row, hi / lo)
+            const int j = J0 + (b >> 1);
+            if (b & 1) p.bl[j] = *(const h8*)(lds + btap + (j + TG) * 128 + 1024);
+            else p.bh[j] = *(const h8*)(lds + btap + (j + TG) * 128);
+        }
+    } else {
+        if (k == 0) p.ah[0] = *(const h8*)(lds + wtap);
+        else if (k == R + 1) p.ah[1] = *(const h8*)(lds + wtap + 512);
+        else p.bh[J0 + k - 1] = *(const h8*)(lds + btap + (J0 + k - 1 + TG) * 128);
+    }
+}
+template <bool SPLIT, int R>
+constexpr int tap_reads() { return SPLIT ? 2 * R + 4 : R + 2; }
+
+// Matrix instruction number q of a tap: 32-tile m, row j, and for SPLIT the term (al*bh, ah*bl, ah*bh in that order).
+template <bool SPLIT, int J0, int J1>
+__device__ __forceinline__ void tap_mfma(const TapOps& p, int q, f32x16 (&acc)[2][4]) {
+    constexpr int R = J1 - J0;
+    if constexpr (SPLIT) {
+        const int m = q / (3 * R), j = J0 + (q / 3) % R, term = q % 3;
+        acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 0 ? p.al[m] : p.ah[m], term == 1 ? p.bl[j] : p.bh[j], acc[m][j], 0, 0, 0);
+    } else {
+        const int m = q / R, j = J0 + q % R;
+        acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p.ah[m], p.bh[j], acc[m][j], 0, 0, 0);
+    }
+}
+template <bool SPLIT, int R>
+constexpr int tap_mfmas() { return SPLIT ? 6 * R : 2 * R; }
+
+// One tap of a main pass: its matrix instructions from `cur`, with the reads of the tap after it (tap group NTG, rows NJ0 .. NJ1 - 1)
+// into `nxt` spread evenly over the first three quarters of them: the wait that opens the next tap is a full one (the compiler counts
+// no LDS reads beside LDS-DMA), and the last quarter gives the last read time to land.  The order is pinned: left to itself the
+// scheduler gathers a tap's reads into one burst right before that wait - measured, the K loop is then 14 % longer
+// (profiles/r16/conv_f16x3_schedule_variants.json).
+template <bool SPLIT, int J0, int J1, int NTG, int NJ0, int NJ1>
+__device__ __forceinline__ void tap_pipelined(const unsigned char* lds, const TapOps& cur, TapOps& nxt, uint32_t nwtap, uint32_t nbtap,
+                                              f32x16 (&acc)[2][4]) {
+    constexpr int NL = tap_reads<SPLIT, NJ1 - NJ0>(), NM = tap_mfmas<SPLIT, J1 - J0>();
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        tap_read<SPLIT, NTG, NJ0, NJ1>(lds, nwtap, nbtap, i, nxt);
+#pragma unroll
+        for (int q = i * (NM - NM / 4) / NL; q < (i + 1 < NL ? (i + 1) * (NM - NM / 4) / NL : NM); ++q) tap_mfma<SPLIT, J0, J1>(cur, q, acc);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The main pass of one stage (tap group TG = dy + 1: three taps dx = -1, 0, +1) of a wave's tile: 2 output-channel tiles x the board
+// rows J0 .. J1 - 1 of its row half.  Row j under tap dy reads board row 4 half + j + dy, which lies (j + TG) * 128 bytes above the
+// row the three per-lane addresses `boff` point at (4 half - 1).  On entry `ops` holds the stage's first tap, on exit the first tap of
+// the NEXT stage's main pass (tap group NTG, rows NJ0 .. NJ1 - 1, weights at nwbase, image at nabase).  Per accumulator the
+// instructions come in the order they always had: tap 0 .. 8, each al*bh, ah*bl, ah*bh.
+template <bool SPLIT, int TG, int J0, int J1, int NTG, int NJ0, int NJ1>
+__device__ __forceinline__ void conv_stage_main(const unsigned char* lds, uint32_t wbase, uint32_t abase, uint32_t nwbase, uint32_t nabase,
+                                                const uint32_t (&boff)[3], f32x16 (&acc)[2][4], TapOps& ops) {
+    TapOps t1, t2;
+    tap_pipelined<SPLIT, J0, J1, TG, J0, J1>(lds, ops, t1, wbase + 8192, abase + boff[1], acc);
+    tap_pipelined<SPLIT, J0, J1, TG, J0, J1>(lds, t1, t2, wbase + 2 * 8192, abase + boff[2], acc);
+    tap_pipelined<SPLIT, J0, J1, NTG, NJ0, NJ1>(lds, t2, ops, nwbase, nabase + boff[0], acc);
+}
+
+// The pass of the row that may be skipped (J1 = J0 + 1), with every tap read in place: same addresses, same order per accumulator.
 template <bool SPLIT, int TG, int J0, int J1>
 __device__ __forceinline__ void conv_stage(const unsigned char* lds, uint32_t wbase, uint32_t abase, const uint32_t (&boff)[3],
                                            f32x16 (&acc)[2][4]) {
@@ -181,9 +275,9 @@ __device__ __forceinline__ void conv_stage(const unsigned char* lds, uint32_t wb
 }
 
 // in / out / skip: split activations (header).  Wl: this layer's region-4 weights.  grid = ceil(n / 8) * F / 128, block 512.
-// Pipeline: stage s+1 (the next tap group's weights, and with the first tap group of a chunk that chunk's activations) is
-// in flight as LDS-DMA into the other buffer while stage s is computed; ONE barrier per stage (it also drains this wave's
-// share of the DMA issued a whole stage earlier).
+// Pipeline: while stage s is computed, stage s+2's weights (and in a chunk's middle stage the next chunk's activations) are in
+// flight as LDS-DMA and stage s+1's first tap is read into registers; ONE barrier per stage (it also drains this wave's share
+// of the DMA issued a whole stage earlier).  The hazard table is in the header.
 // SPLIT: true = raznet-forward-v2 (hi and lo halfs, three matrix instructions per product); false = v3 (hi halfs alone, one).
 template <bool SPLIT>
 __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* __restrict__ Wl, const float* __restrict__ bias,
@@ -236,10 +330,9 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
     // position's four activation planes of that chunk.  !SPLIT: the 12 hi pieces alone (piece p holds the hi halfs when p & 2 is
     // clear: hi piece j is piece (j >> 1) * 4 + (j & 1); every wave moves hi piece wv, waves 0-3 also hi piece 8 + wv) and the two
     // hi planes (0 and 2), to the places they have in the v2 image
-    auto issue = [&](int c, int tg) {
-        const int st = c * 3 + tg;
-        const unsigned char* src = wsrc + (size_t)st * W_STAGE;
-        unsigned char* dst = lds + LDS_W + (st & 1) * W_STAGE;
+    auto issue_w = [&](int c, int tg) {   // into weight buffer tg
+        const unsigned char* src = wsrc + (size_t)(c * 3 + tg) * W_STAGE;
+        unsigned char* dst = lds + LDS_W + tg * W_STAGE;
         if constexpr (SPLIT) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) GLDS16(src + (wv * 3 + i) * 1024, dst + (wv * 3 + i) * 1024);
@@ -248,36 +341,54 @@ __global__ __launch_bounds__(512, 2) void k_conv3x3_f16x3(const unsigned char* _
             GLDS16(src + p0w * 1024, dst + p0w * 1024);
             if (wv < 4) GLDS16(src + (p0w + 16) * 1024, dst + (p0w + 16) * 1024);   // hi piece 8 + wv = piece 16 + p0w
         }
-        if (tg == 0) {
-            const unsigned char* a = asrc + (size_t)c * ACT_POS;
-            unsigned char* ad = lds + LDS_ACT + (c & 1) * ACT_IMG + act_pos_off(wv);
-#pragma unroll
-            for (int pl = 0; pl < 4; pl += SPLIT ? 1 : 2) GLDS16(a + pl * 1024, ad + pl * 1024);
-        }
     };
-    issue(0, 0);
-    for (int c = 0; c < nchunks; ++c) {
-        const uint32_t abase = (uint32_t)(LDS_ACT + (c & 1) * ACT_IMG);
+    auto issue_a = [&](int c) {   // into image c & 1
+        const unsigned char* a = asrc + (size_t)c * ACT_POS;
+        unsigned char* ad = lds + LDS_ACT + (c & 1) * ACT_IMG + act_pos_off(wv);
 #pragma unroll
-        for (int tg = 0; tg < 3; ++tg) {
-            const int st = c * 3 + tg;
+        for (int pl = 0; pl < 4; pl += SPLIT ? 1 : 2) GLDS16(a + pl * 1024, ad + pl * 1024);
+    };
+    // The stage stream (hazard table in the header).  Weights run TWO stages ahead in three buffers, so at barrier st + 1 stage
+    // st + 1 has been in LDS since barrier st, and the last tap of stage st reads its first tap (`ops`) before that barrier: after
+    // it the matrix instructions start from registers.  A chunk's activations are issued in the middle stage of the chunk before.
+    const uint32_t w0 = (uint32_t)LDS_W + aoff, w1 = w0 + W_STAGE, w2 = w1 + W_STAGE;
+    issue_w(0, 0);
+    issue_a(0);
+    issue_w(0, 1);
+    RAZ_STAMP_BARRIER_IN;
+    __syncthreads();   // barrier 0: stages 0 and 1, image 0 and the zero areas are in LDS
+    RAZ_STAMP_BARRIER_OUT(0);
+    TapOps ops;   // the first tap of the coming stage's main pass
+#pragma unroll
+    for (int k = 0; k < tap_reads<SPLIT, 3>(); ++k) tap_read<SPLIT, 0, 1, 4>(lds, w0, (uint32_t)LDS_ACT + boff[0], k, ops);
+    for (int c = 0; c < nchunks; ++c) {
+        const uint32_t abase = (uint32_t)(LDS_ACT + (c & 1) * ACT_IMG), nabase = (uint32_t)(LDS_ACT + (~c & 1) * ACT_IMG);
+        const bool more = c + 1 < nchunks;   // (uniform over the workgroup)
+        // dy = -1 of board row 0 and dy = +1 of board row 7 are whole all-zero B operands: not read, not issued
+        // (the row that may be skipped is a pass of its own over the stage's taps: only its two accumulators cross the branch)
+        // stage (c, 0): barrier 3 c has been passed
+        issue_w(c, 2);
+        conv_stage_main<SPLIT, 0, 1, 4, 1, 0, 4>(lds, w0, abase, w1, abase, boff, acc, ops);
+        if (half != 0) conv_stage<SPLIT, 0, 0, 1>(lds, w0, abase, boff, acc);
+        RAZ_STAMP_BARRIER_IN;
+        __syncthreads();   // barrier 3 c + 1: stage (c, 2) has landed (every wave drained its DMA before arriving); buffer 0 and, if c > 0, image c - 1 are free
+        RAZ_STAMP_BARRIER_OUT(3 * c + 1);
+        if (more) {
+            issue_w(c + 1, 0);
+            issue_a(c + 1);
+        }
+        conv_stage_main<SPLIT, 1, 0, 4, 2, 0, 3>(lds, w1, abase, w2, abase, boff, acc, ops);
+        RAZ_STAMP_BARRIER_IN;
+        __syncthreads();   // barrier 3 c + 2: stage (c + 1, 0) and image c + 1 have landed; buffer 1 is free
+        RAZ_STAMP_BARRIER_OUT(3 * c + 2);
+        if (more) issue_w(c + 1, 1);
+        // (after the last chunk the read-ahead takes what lies in buffer 0 and the other image: nothing is in flight there and nobody uses it)
+        conv_stage_main<SPLIT, 2, 0, 3, 0, 1, 4>(lds, w2, abase, w0, nabase, boff, acc, ops);
+        if (half != 1) conv_stage<SPLIT, 2, 3, 4>(lds, w2, abase, boff, acc);
+        if (more) {
             RAZ_STAMP_BARRIER_IN;
-            __syncthreads();   // stage st has landed (every wave drained its DMA before arriving); stage st-1's reads are done
-            RAZ_STAMP_BARRIER_OUT(st);
-            if (tg < 2) issue(c, tg + 1);
-            else if (c + 1 < nchunks) issue(c + 1, 0);
-            const uint32_t wbase = (uint32_t)(LDS_W + (st & 1) * W_STAGE) + aoff;
-            // dy = -1 of board row 0 and dy = +1 of board row 7 are whole all-zero B operands: not read, not issued
-            // (the row that may be skipped is a pass of its own over the stage's taps: only its two accumulators cross the branch)
-            if (tg == 0) {
-                conv_stage<SPLIT, 0, 1, 4>(lds, wbase, abase, boff, acc);
-                if (half != 0) conv_stage<SPLIT, 0, 0, 1>(lds, wbase, abase, boff, acc);
-            } else if (tg == 1) {
-                conv_stage<SPLIT, 1, 0, 4>(lds, wbase, abase, boff, acc);
-            } else {
-                conv_stage<SPLIT, 2, 0, 3>(lds, wbase, abase, boff, acc);
-                if (half != 1) conv_stage<SPLIT, 2, 3, 4>(lds, wbase, abase, boff, acc);
-            }
+            __syncthreads();   // barrier 3 c + 3: stage (c + 1, 1) has landed; buffer 2 is free
+            RAZ_STAMP_BARRIER_OUT(3 * c + 3);
         }
     }
     RAZ_STAMP_AT(2);

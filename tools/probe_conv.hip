@@ -36,6 +36,11 @@ int raz_net_repair_rows(const float*, int, int, int, const uint64_t*, const uint
 int raz_fail(int code, const char* msg) { fprintf(stderr, "raz_fail %d: %s\n", code, msg); return code; }
 int raz_fail_hip(hipError_t e, const char* where) { fprintf(stderr, "hip error %s at %s\n", hipGetErrorString(e), where); return RAZ_EDEVICE; }
 int raz_check_launch(const char* where) { hipError_t e = hipGetLastError(); return e == hipSuccess ? RAZ_OK : raz_fail_hip(e, where); }
+// (raz_capi.hip's, which the probe does not link: the forward's launcher refers to it, the probe opts its kernel in itself)
+int raz_lds_opt_in(const void* kernel, size_t bytes, const char* where) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return e == hipSuccess ? RAZ_OK : raz_fail_hip(e, where);
+}
 
 #define CK(x)                                                                                 \
     do {                                                                                      \
