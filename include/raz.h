@@ -698,6 +698,107 @@ int raz_match_turn(raz_match* m, raz_stream_t stream);
 int raz_match_stats_sync(raz_match* m, raz_match_stats* out, raz_stream_t stream);
 int raz_match_read(raz_match* m, raz_match_game* games, raz_match_ply* log, uint32_t* log_root_n, raz_stream_t stream);
 
+/* ---- retrograde analysis of whole games on the device (csrc/raz_analysis.h) ----------------------------------------
+ * The NBoard command the reference leaves as `pass` (play_game/nboard.py:321-330: "for each board position occurring in the game the
+ * engine sends back ... {movesMade} {eval}"), for n_games games at once.  Game g is a start position and a list of at most max_moves
+ * entries; P = max_moves + 1; position (g, j) is the position after j entries and belongs to slot first_slot + g * P + j of ONE started
+ * engine created with record_root_w, which searches it with the tree, random streams and one-move semantics
+ * raz_engine_set_position gives that slot.  The caller steps the engine.  The analysis lives in a caller-provided device workspace
+ * (raz_analysis_workspace_bytes(n_games, max_moves) bytes, 256-byte aligned, owned by the caller, as is the engine, for the lifetime
+ * of the handle; 0 is returned for n_games == 0 or max_moves outside 1..127):
+ *   raz_analysis_stats u32[8] | raz_analysis_game [n_games] | raz_analysis_pos [n_games][P] | raz_analysis_eval [n_games][P],
+ *   each section rounded up to 256 bytes.
+ * raz_analysis_start: game g starts on (d_black[g], d_white[g], d_player[g] 1 black / 2 white to move) - the three arrays are
+ *   nullable, all or none: NULL = the initial position, black to move; the caller guarantees playable positions - and plays
+ *   d_moves[g][0 .. max_moves): 0..63 a move, -1 a pass entry ("PA"), -2 the end of the list; any other value ends the list and sets
+ *   RAZ_ANALYSIS_ERR_BAD_CODE in the game's summary and the stats.  One launch, one thread per game, clears the workspace and walks
+ *   every list as NBoardEngine.set_game does (nboard.py:96-103: env.update, then env.step(action) for every entry that is not a pass
+ *   entry) under ReversiEnv.step's rules (env/reversi_env.py:42-104: the automatic pass, game over when neither side can move,
+ *   illegal_move_to_lose on a move that flips nothing).  It writes the position before every entry, the game's summary, and arms the
+ *   slot of every SEARCH position: the mover's own discs as "black", player 1, `sims` simulations, one move, no resignation
+ *   (nboard.py:50).  Every other slot of the range is left untouched.  Entries after the game is over are IGNORED - the reference
+ *   would go on stepping a finished env; that is not reproduced.
+ * raz_analysis_collect: one launch, one wave per position.  A pending position whose slot has decided (phase idle, one ply recorded -
+ *   raz_match_turn's rule) gets its eval: the engine's action, the sum of the root's visit counts, the up to RAZ_ANALYSIS_TOP squares
+ *   with n > 0 by visit count descending (lowest square first among equals) with n and q = w / ((double)n + 1e-5)
+ *   (ReversiPlayer.var_q, agent/player.py:62-64), and the same pair for the entry played from the position (0, 0.0 where that is no
+ *   move).  A slot the root solver answered (ply header flag bit 0) gives state SOLVED and ONE entry: the action with the header's
+ *   exact n and q (sum_n = that n; the played pair is that pair where the entry is the action, else 0, 0.0).  A slot still searching
+ *   is left pending.  A slot that carries an engine error flag, or that left the one-move protocol, gives state ERROR and ORs the
+ *   flags / RAZ_ANALYSIS_ERR_SLOT into the stats' error word: an analysis never spins.  A position already collected is not written
+ *   again, and no position waits for another.
+ * raz_analysis_stats_sync: the counters (synchronises `stream`).  raz_analysis_read: the games, positions and evals to host arrays of
+ *   n_games, n_games x P and n_games x P entries (any may be NULL; synchronises `stream`).
+ * RAZ_EINVAL / RAZ_ESTATE with a message and NO launch: a NULL argument, an engine that is not started or was created without
+ *   record_root_w, first_slot + n_games x P beyond the engine's slots, a workspace that is NULL, misaligned or short, sims of 0,
+ *   max_moves outside 1..127, position arrays given in part, collect / stats / read before start. */
+typedef struct raz_analysis raz_analysis;
+#define RAZ_ANALYSIS_TOP 8
+#define RAZ_ANALYSIS_MAX_MOVES 127
+#define RAZ_ANALYSIS_ENTRY_PASS (-1)
+#define RAZ_ANALYSIS_ENTRY_END (-2)
+#define RAZ_ANALYSIS_POS_NONE 0         /* beyond the list, or beyond the end of the game */
+#define RAZ_ANALYSIS_POS_SEARCH 1       /* its slot was armed */
+#define RAZ_ANALYSIS_POS_PASS_ENTRY 2   /* the entry from here is a pass entry: the position is the one after it too, searched there */
+#define RAZ_ANALYSIS_POS_OVER 3         /* the game ended here, by the rules or by an illegal move */
+#define RAZ_ANALYSIS_END_LIST 0         /* the list ended with the game running */
+#define RAZ_ANALYSIS_END_RULES 1        /* neither side could move */
+#define RAZ_ANALYSIS_END_ILLEGAL 2      /* a move that flips nothing: the mover lost (reversi_env.py:90-93) */
+#define RAZ_ANALYSIS_EVAL_NONE 0        /* not a SEARCH position */
+#define RAZ_ANALYSIS_EVAL_PENDING 1
+#define RAZ_ANALYSIS_EVAL_SEARCHED 2
+#define RAZ_ANALYSIS_EVAL_SOLVED 3
+#define RAZ_ANALYSIS_EVAL_ERROR 4
+#define RAZ_ANALYSIS_ERR_SLOT 0x100u       /* a slot finished outside the one-move protocol (phase done, or idle without exactly one ply) */
+#define RAZ_ANALYSIS_ERR_BAD_CODE 0x400u   /* a list entry outside -2..63 */
+typedef struct {
+    uint64_t black, white;       /* the board, absolute colours */
+    uint8_t player;              /* side to move: 1 black / 2 white */
+    uint8_t state;               /* RAZ_ANALYSIS_POS_* */
+    uint8_t moves_made;          /* j */
+    int8_t played;               /* the entry played from here: 0..63, -1 a pass entry, -2 none */
+    uint32_t pad;
+} raz_analysis_pos;              /* 24 bytes */
+typedef struct {
+    uint32_t positions;          /* positions written (states other than NONE): 1 + the entries played */
+    uint8_t ended;               /* RAZ_ANALYSIS_END_* */
+    uint8_t winner;              /* 0 running; 1 black / 2 white / 3 draw */
+    uint8_t blacks, whites;      /* disc counts of the last position */
+    uint32_t errors;             /* 0 or RAZ_ANALYSIS_ERR_BAD_CODE */
+    uint32_t searched;           /* SEARCH positions: slots armed */
+} raz_analysis_game;             /* 16 bytes */
+typedef struct {
+    uint8_t state;               /* RAZ_ANALYSIS_EVAL_* */
+    int8_t action;               /* the engine's move: 0..63, -1 = resigned / none */
+    uint8_t n_top;               /* entries of top_* in use */
+    int8_t played;               /* raz_analysis_pos.played */
+    uint32_t sum_n;              /* sum of the root's visit counts */
+    double top_q[RAZ_ANALYSIS_TOP];
+    uint32_t top_n[RAZ_ANALYSIS_TOP];
+    int8_t top_square[RAZ_ANALYSIS_TOP];
+    double played_q;
+    uint32_t played_n;
+    uint32_t flags;              /* state ERROR: the slot's engine error flags | RAZ_ANALYSIS_ERR_SLOT */
+} raz_analysis_eval;             /* 128 bytes */
+typedef struct {
+    uint32_t games;              /* games replayed by raz_analysis_start */
+    uint32_t positions;          /* positions written */
+    uint32_t armed;              /* SEARCH positions */
+    uint32_t pending;            /* of those, not yet collected */
+    uint32_t searched, solved, failed;   /* collected, by eval state */
+    uint32_t error;              /* 0, or engine error flags of a slot (1 pool, 2 table, 4 records, 8 path) | RAZ_ANALYSIS_ERR_* */
+} raz_analysis_stats;            /* 32 bytes */
+size_t raz_analysis_workspace_bytes(uint32_t n_games, uint32_t max_moves);
+int raz_analysis_create(raz_engine* engine, uint32_t first_slot, void* d_workspace, size_t workspace_bytes, uint32_t n_games,
+                        uint32_t max_moves, raz_analysis** out);
+void raz_analysis_destroy(raz_analysis* a);
+int raz_analysis_start(raz_analysis* a, const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player,
+                       const int8_t* d_moves, uint32_t sims, raz_stream_t stream);
+int raz_analysis_collect(raz_analysis* a, raz_stream_t stream);
+int raz_analysis_stats_sync(raz_analysis* a, raz_analysis_stats* out, raz_stream_t stream);
+int raz_analysis_read(raz_analysis* a, raz_analysis_game* games, raz_analysis_pos* positions, raz_analysis_eval* evals,
+                      raz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ class RazMatchStats(ctypes.Structure):
                 ("error", c_uint32), ("pad", c_uint32 * 3)]
 
 
+class RazAnalysisStats(ctypes.Structure):
+    _fields_ = [("games", c_uint32), ("positions", c_uint32), ("armed", c_uint32), ("pending", c_uint32),
+                ("searched", c_uint32), ("solved", c_uint32), ("failed", c_uint32), ("error", c_uint32)]
+
+
 SIGNATURES.update({
     "raz_net_weight_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raz_net_scratch_bytes": (c_size_t, [c_int, c_int, c_size_t]),
@@ -171,6 +176,14 @@ SIGNATURES.update({
     "raz_match_turn": (c_int, [c_void_p, c_void_p]),
     "raz_match_stats_sync": (c_int, [c_void_p, POINTER(RazMatchStats), c_void_p]),
     "raz_match_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # retrograde analysis of whole games on the device (csrc/raz_analysis.h); the handle travels as c_void_p
+    "raz_analysis_workspace_bytes": (c_size_t, [c_uint32, c_uint32]),
+    "raz_analysis_create": (c_int, [c_void_p, c_uint32, c_void_p, c_size_t, c_uint32, c_uint32, POINTER(c_void_p)]),
+    "raz_analysis_destroy": (None, [c_void_p]),
+    "raz_analysis_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "raz_analysis_collect": (c_int, [c_void_p, c_void_p]),
+    "raz_analysis_stats_sync": (c_int, [c_void_p, POINTER(RazAnalysisStats), c_void_p]),
+    "raz_analysis_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

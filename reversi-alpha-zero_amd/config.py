@@ -1,6 +1,6 @@
 """Hyper-parameter tree with the reference's names and default values (reversi_zero/config.py:15-193)
-for the sections the workers read: play, play_data, model, trainer, eval, resource (+ opts).  The GUI
-section of the reference is not restated.
+for the sections the workers and the play_game front-ends read: play, play_data, model, trainer, eval,
+play_with_human, nboard, resource (+ opts).  The wx window's section (gui) is not restated.
 
 `load_config(yml_path)` overlays a reference YAML file (config/*.yml) the way
 manager.py:41-45 + moke_config.create_config do: recursive attribute assignment, unknown sections
@@ -100,6 +100,28 @@ class PlayConfig(_Section):
         self.use_newest_next_generation_model = True
 
 
+class PlayWithHumanConfig(_Section):
+    def __init__(self):  # config.py:74-80
+        self.parallel_search_num = 8
+        self.noise_eps = 0
+        self.change_tau_turn = 0
+        self.resign_threshold = None
+        self.use_newest_next_generation_model = True
+
+    def update_play_config(self, pc):
+        """config.py:82-92: an interactive game is played without root noise, by the most visited move, without resigning."""
+        for name in ("noise_eps", "change_tau_turn", "parallel_search_num", "resign_threshold", "use_newest_next_generation_model"):
+            setattr(pc, name, getattr(self, name))
+
+
+class NBoardConfig(_Section):
+    def __init__(self):  # config.py:95-100
+        self.my_name = "RAZ"
+        self.read_stdin_timeout = 0.1
+        self.simulation_num_per_depth_about = 20
+        self.hint_callback_per_sim = 10
+
+
 class EvaluateConfig(_Section):
     """config.py:101-110.  play_config.parallel_search_num stays at the PlayConfig default (8), as in the
     reference; the engine plays it on the deterministic raz-sched-v1 schedule."""
@@ -149,6 +171,8 @@ class Config(_Section):
         self.play_data = PlayDataConfig()
         self.trainer = TrainerConfig()
         self.eval = EvaluateConfig()
+        self.play_with_human = PlayWithHumanConfig()
+        self.nboard = NBoardConfig()
 
 
 def load_config(yml_path=None, overrides=None):

@@ -1069,6 +1069,7 @@ extern "C" int raz_engine_set_positions(raz_engine* e, uint32_t first_slot, uint
 }
 
 #include "raz_match.h"   // evaluation matches on the device: the hand-off between two engines (raz_match_*)
+#include "raz_analysis.h"   // retrograde analysis of whole games on the device: replay, arming and reduction (raz_analysis_*)
 
 // Prune unreachable nodes (positions with fewer discs than the current real position) in every
 // game whose pool holds at least `threshold` nodes.  Asynchronous on `stream`; call between

@@ -727,6 +727,107 @@ class DeviceMatch:
         return match_games(*self.read(), first_game_id=first_game_id)
 
 
+ANALYSIS_GAME = np.dtype([("positions", "<u4"), ("ended", "u1"), ("winner", "u1"), ("blacks", "u1"), ("whites", "u1"), ("errors", "<u4"),
+                          ("searched", "<u4")])
+ANALYSIS_POS = np.dtype([("black", "<u8"), ("white", "<u8"), ("player", "u1"), ("state", "u1"), ("moves_made", "u1"), ("played", "i1"),
+                         ("pad", "<u4")])
+ANALYSIS_TOP = 8         # include/raz.h RAZ_ANALYSIS_TOP
+ANALYSIS_MAX_MOVES = 127
+ANALYSIS_EVAL = np.dtype([("state", "u1"), ("action", "i1"), ("n_top", "u1"), ("played", "i1"), ("sum_n", "<u4"),
+                          ("top_q", "<f8", (ANALYSIS_TOP,)), ("top_n", "<u4", (ANALYSIS_TOP,)), ("top_square", "i1", (ANALYSIS_TOP,)),
+                          ("played_q", "<f8"), ("played_n", "<u4"), ("flags", "<u4")])
+assert ANALYSIS_GAME.itemsize == 16 and ANALYSIS_POS.itemsize == 24 and ANALYSIS_EVAL.itemsize == 128
+ANALYSIS_ENTRY_PASS, ANALYSIS_ENTRY_END = -1, -2                                     # list entries beside the moves 0..63
+POS_NONE, POS_SEARCH, POS_PASS_ENTRY, POS_OVER = 0, 1, 2, 3                           # RAZ_ANALYSIS_POS_*
+EVAL_NONE, EVAL_PENDING, EVAL_SEARCHED, EVAL_SOLVED, EVAL_ERROR = 0, 1, 2, 3, 4      # RAZ_ANALYSIS_EVAL_*
+ANALYSIS_ERR_SLOT, ANALYSIS_ERR_BAD_CODE = 0x100, 0x400
+
+
+def analysis_error_text(error):
+    return (f"analysis error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
+            f"0x100 a slot left the one-move protocol, 0x400 a list entry outside -2..63)")
+
+
+class DeviceAnalysis:
+    """The retrograde analysis of whole games on one started engine created with record_root_w (include/raz.h raz_analysis_*):
+    position j of game g - the position after j list entries - is searched by slot first_slot + g * (max_moves + 1) + j.  The caller
+    steps the engine; collect() reduces every decided search where it lies, without a host round trip."""
+
+    def __init__(self, engine, first_slot=0, workspace=None):
+        """workspace: a uint8 device tensor to keep the analysis in (None: the analysis's own, sized by every start)."""
+        self.engine, self.device, self.first_slot = engine, engine.device, int(first_slot)
+        self._given, self._ws, self._h = workspace, None, ctypes.c_void_p()
+        self.n_games = self.max_moves = 0
+
+    def _destroy(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib.raz_analysis_destroy(h)
+            self._h = ctypes.c_void_p()
+
+    __del__ = _destroy
+
+    def start(self, moves, positions=None, sims=None):
+        """moves: int8 device tensor [n_games, max_moves] (0..63 a move, -1 a pass entry, -2 the end of the list).  positions: None
+        (the initial position, black to move) or (black int64, white int64, player uint8) device tensors [n_games].  sims:
+        simulations a move."""
+        import torch
+        if not (isinstance(moves, torch.Tensor) and moves.is_cuda and moves.is_contiguous() and moves.dtype == torch.int8 and moves.dim() == 2):
+            raise ValueError("DeviceAnalysis.start takes a contiguous int8 device tensor [n_games, max_moves] (no CPU tensors)")
+        n, mm = int(moves.shape[0]), int(moves.shape[1])
+        if positions is not None:
+            if len(positions) != 3:
+                raise ValueError("positions is (black, white, player)")
+            for t in positions:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
+                    raise ValueError("DeviceAnalysis.start takes contiguous device tensors of n_games entries (no CPU tensors)")
+            if positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8:
+                raise ValueError("positions: int64, int64, uint8")
+        if not sims:
+            raise ValueError("sims: simulations a move")
+        if (n, mm) != (self.n_games, self.max_moves) or not self._h:
+            self._destroy()
+            need = lib.raz_analysis_workspace_bytes(n, mm)
+            if not need:
+                raise ValueError("DeviceAnalysis.start: " + N.last_error())
+            ws = self._given if self._given is not None else (
+                self._ws if self._ws is not None and self._ws.numel() >= need + 256 else torch.zeros(need + 256, dtype=torch.uint8, device=self.device))
+            base = (ws.data_ptr() + 255) // 256 * 256
+            if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and base + need <= ws.data_ptr() + ws.numel()):
+                raise ValueError("workspace: a contiguous uint8 device tensor with workspace_bytes behind its first 256-byte boundary")
+            self._ws, self.workspace_base, self.workspace_bytes = ws, base, need
+            check(lib.raz_analysis_create(self.engine._h, self.first_slot, base, need, n, mm, ctypes.byref(self._h)), "raz_analysis_create")
+            self.n_games, self.max_moves = n, mm
+        self._args = [moves] + list(positions or ())   # (kept alive until the launch has run)
+        b, w, p = (t.data_ptr() for t in positions) if positions is not None else (None, None, None)
+        with torch.cuda.device(self.device):
+            check(lib.raz_analysis_start(self._h, b, w, p, moves.data_ptr(), int(sims), _stream()), "raz_analysis_start")
+
+    def collect(self):
+        import torch
+        with torch.cuda.device(self.device):
+            check(lib.raz_analysis_collect(self._h, _stream()), "raz_analysis_collect")
+
+    def stats(self, raise_on_error=True):
+        """{"games", "positions", "armed", "pending", "searched", "solved", "failed", "error"}; raises on the error word.  Synchronises."""
+        import torch
+        st = N.RazAnalysisStats()
+        with torch.cuda.device(self.device):
+            check(lib.raz_analysis_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_analysis_stats_sync")
+        if st.error and raise_on_error:
+            raise RuntimeError(analysis_error_text(st.error))
+        return {k: getattr(st, k) for k, _ in N.RazAnalysisStats._fields_}
+
+    def results(self):
+        """(ANALYSIS_GAME [n], ANALYSIS_POS [n, max_moves + 1], ANALYSIS_EVAL [n, max_moves + 1]) on the host.  Synchronises."""
+        import torch
+        n, P = self.n_games, self.max_moves + 1
+        games, pos, evals = np.zeros(n, dtype=ANALYSIS_GAME), np.zeros((n, P), dtype=ANALYSIS_POS), np.zeros((n, P), dtype=ANALYSIS_EVAL)
+        with torch.cuda.device(self.device):
+            check(lib.raz_analysis_read(self._h, games.ctypes.data, pos.ctypes.data, evals.ctypes.data, _stream()), "raz_analysis_read")
+        return games, pos, evals
+
+
 GAME_SUMMARY = np.dtype([("final_black", "<u8"), ("final_white", "<u8"), ("game_id", "<u4"), ("n_plies", "<u4"),
                          ("status", "u1"), ("resigned_black", "u1"), ("resigned_white", "u1"), ("enable_resign", "u1"),
                          ("sims", "<u4")])

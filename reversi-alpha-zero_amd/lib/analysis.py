@@ -1,0 +1,119 @@
+"""Retrograde analysis of whole games on the device: every position of every game searched by a slot of ONE engine at once
+(include/raz.h raz_analysis_*, engine.DeviceAnalysis).  The NBoard command the reference leaves as `pass`
+(reversi_zero/play_game/nboard.py:321-330), and the annotation of files of games such as data/self_play-ggf/*.ggf."""
+from logging import getLogger
+from types import SimpleNamespace
+
+import numpy as np
+
+from ..agent.player import effective_play_config
+from ..engine import (ANALYSIS_ENTRY_END, ANALYSIS_ENTRY_PASS, ANALYSIS_MAX_MOVES, EVAL_SOLVED, POS_OVER, POS_PASS_ENTRY, POS_SEARCH,
+                      DeviceAnalysis, DeviceNet, SelfPlayEngine)
+from .ggf import convert_to_bitboard_and_actions, parse_ggf
+
+logger = getLogger(__name__)
+
+# engine steps between two collects, and collects between two reads of the counters: their product is the horizon of the pool check
+# (64 steps), as worker/evaluate.py's device route splits it
+STEPS_PER_COLLECT = 8
+COLLECTS_PER_STATS = 8
+
+
+def game_from_ggf(text):
+    """(black, white, player, actions) of a GGF string."""
+    ggf = parse_ggf(text)
+    black, white, actions = convert_to_bitboard_and_actions(ggf)
+    return black, white, 1 if ggf.BO.color == "*" else 2, actions
+
+
+def positions_of(pos, evals):
+    """One game's per-position dictionaries from its ANALYSIS_POS / ANALYSIS_EVAL rows (engine.DeviceAnalysis.results)."""
+    out = []
+    for p, e in zip(pos, evals):
+        state = int(p["state"])
+        if state == 0:
+            break
+        d = {"moves_made": int(p["moves_made"]), "player": int(p["player"]), "black": int(p["black"]), "white": int(p["white"]),
+             "state": {POS_SEARCH: "search", POS_PASS_ENTRY: "pass_entry", POS_OVER: "over"}[state],
+             "played": None if int(p["played"]) < 0 else int(p["played"])}
+        if state == POS_SEARCH:
+            k = int(e["n_top"])
+            d.update(eval=float(e["top_q"][0]) if k else 0.0, best_move=int(e["top_square"][0]) if k else None,
+                     visits=int(e["sum_n"]), action=None if int(e["action"]) < 0 else int(e["action"]), exact=int(e["state"]) == EVAL_SOLVED,
+                     top=[(int(e["top_square"][i]), int(e["top_n"][i]), float(e["top_q"][i])) for i in range(k)])
+            if d["played"] is not None:
+                d.update(played_eval=float(e["played_q"]), played_visits=int(e["played_n"]), played_diff=float(e["played_q"]) - d["eval"])
+        elif state == POS_OVER:
+            nb, nw = bin(d["black"]).count("1"), bin(d["white"]).count("1")
+            d.update(discs=(nb, nw), disc_diff=(nb - nw) if d["player"] == 1 else (nw - nb))
+        out.append(d)
+    for i, d in enumerate(out):   # a pass entry's position is the one after it: it repeats that position's search
+        if d["state"] == "pass_entry":
+            nxt = next((x for x in out[i + 1:] if x["state"] != "pass_entry"), None)
+            if nxt is not None:
+                d.update({k: v for k, v in nxt.items() if k in ("eval", "best_move", "visits", "action", "exact", "top", "discs", "disc_diff")})
+    return out
+
+
+class GameAnalyzer:
+    """analyze(games): per game a list of per-position dictionaries - moves_made, player (side to move), eval (the most visited
+    move's value, from the side to move's view), best_move, visits, top; played_eval / played_diff for the move that was played;
+    exact where the end-game solver answered."""
+
+    def __init__(self, config, model, play_config=None, slots=1024, device="cuda:0", seed=0):
+        self.config, self.device, self.slots, self.seed = config, device, int(slots), seed
+        self.play_config = effective_play_config(config, play_config)
+        m = getattr(model, "model", model)
+        self.net = m if isinstance(m, DeviceNet) else DeviceNet(m.to_blob(), device)
+        self.sims = int(self.play_config.simulation_num_per_move)
+        shim = SimpleNamespace(play=self.play_config, play_data=config.play_data)
+        loops = max(1, int(self.play_config.thinking_loop))
+        # a slot searches ONE move: a node and its mirror per simulation, not the 62 plies of a game
+        self.engine = SelfPlayEngine(shim, self.net, self.slots, seed=seed, nodes_per_game=(self.sims * loops + 64) * 2 + 128,
+                                     sims_hint=self.sims, max_plies=64, record_root_w=True, single_stream=True, parts=1)
+        self.engine.start(0, self.sims, n_active=0)
+        self.analysis = DeviceAnalysis(self.engine)
+        self.passes = 0
+
+    def _busy(self):
+        eng = self.engine
+        st = eng.stats()   # raises on engine error flags
+        if eng.pool_nearly_full(st, STEPS_PER_COLLECT * COLLECTS_PER_STATS):
+            eng.gc(threshold=min(int(eng.cfg.nodes_per_game) // 4, st["max_pool_used"] // 2))
+
+    def analyze(self, games):
+        import torch
+        games = [game_from_ggf(g) if isinstance(g, str) else tuple(g) for g in games]
+        if not games:
+            return []
+        lists = [[ANALYSIS_ENTRY_PASS if a is None else int(a) for a in g[3]] for g in games]
+        mm = max(1, max(len(x) for x in lists))
+        if mm > ANALYSIS_MAX_MOVES:
+            raise ValueError(f"a game of {mm} entries: at most {ANALYSIS_MAX_MOVES}")
+        P = mm + 1
+        per_pass = self.slots // P
+        if per_pass < 1:
+            raise ValueError(f"{self.slots} slots cannot hold the {P} positions of one game")
+        out = []
+        for lo in range(0, len(games), per_pass):
+            chunk = range(lo, min(lo + per_pass, len(games)))
+            moves = np.full((len(chunk), mm), ANALYSIS_ENTRY_END, dtype=np.int8)
+            for i, g in enumerate(chunk):
+                moves[i, :len(lists[g])] = lists[g]
+            u = lambda xs: torch.from_numpy(np.array(xs, dtype=np.uint64).view(np.int64)).to(self.device)
+            pos = (u([games[g][0] for g in chunk]), u([games[g][1] for g in chunk]),
+                   torch.tensor([int(games[g][2]) for g in chunk], dtype=torch.uint8, device=self.device))
+            an = self.analysis
+            self.engine.start(lo * P, self.sims, n_active=0)   # empty trees, fresh random streams: a pass does not depend on the ones before it
+            an.start(torch.from_numpy(moves).to(self.device), pos, self.sims)
+            st = an.stats()   # raises on the error word
+            while st["pending"]:
+                for _ in range(COLLECTS_PER_STATS):
+                    self.engine.step(STEPS_PER_COLLECT)
+                    an.collect()
+                self._busy()
+                st = an.stats()
+            _, p, e = an.results()
+            out += [positions_of(p[i], e[i]) for i in range(len(chunk))]
+            self.passes += 1
+        return out
