@@ -799,6 +799,86 @@ int raz_analysis_stats_sync(raz_analysis* a, raz_analysis_stats* out, raz_stream
 int raz_analysis_read(raz_analysis* a, raz_analysis_game* games, raz_analysis_pos* positions, raz_analysis_eval* evals,
                       raz_stream_t stream);
 
+/* ---- a league of up to 16 models on the device (csrc/raz_league.h) ---------------------------------------------------
+ * raz_match_* with the pairing of every game spelled out.  A league couples n_models (2..RAZ_LEAGUE_MAX_MODELS) STARTED engines, one
+ * per model, which may differ in n_games, and plays n_games games at once: game g names its two models and, for each, the slot of that
+ * model's engine that is its player in the game (raz_league_pairing), with the tree, random streams and one-move semantics
+ * raz_engine_set_position gives that slot.  The caller steps the engines.  The league lives in a caller-provided device workspace
+ * (raz_league_workspace_bytes(n_models, slots_per_model, n_games) bytes, slots_per_model[m] = engine m's n_games; 256-byte aligned,
+ * owned by the caller, as are the engines, for the lifetime of the handle; 0 is returned, with a message, for n_models outside 2..16,
+ * n_games == 0 or a NULL array):
+ *   raz_league_stats and the models' simulations a move u32[16] | raz_engine_dev [n_models] (the engines' descriptors: a table in
+ *   HBM, not kernel arguments) |
+ *   raz_league_pairing [n_games] | raz_league_game [n_games] | raz_league_ply [n_games][64] | one u32 claim word per slot of every
+ *   engine | root visit counts u32 [n_games][64][64], each section rounded up to 256 bytes.
+ * raz_league_start: memsets of the counters, games, log headers and claim words, the descriptor table written on `stream`, and two
+ *   launches of one thread per game.  The first copies d_pairings[g] into the workspace (the caller's array need not outlive the call's
+ *   work on `stream`) and, where the pairing is SOUND - both model indices < n_models and different, both slots < their engine's
+ *   n_games - does atomicMin(claim[model][slot], g) on both slots.  The second starts game g where its pairing is sound AND both claim
+ *   words hold g: the lowest game index wins a contested slot, whatever the launch order.  A game not started gets
+ *   RAZ_LEAGUE_GAME_NOT_STARTED and searching 0, is never counted live, and RAZ_LEAGUE_ERR_PAIRING goes into the error word.  Every
+ *   other game starts as raz_match_start starts one: (d_black[g], d_white[g], d_player[g]) - nullable, all or none: NULL = the initial
+ *   position, black to move; playable positions are the caller's guarantee - with the side to move armed in its model's engine at its
+ *   slot: the mover's own discs as "black", player 1, sims_per_model[model] (a HOST array of n_models entries) simulations, one move.
+ *   Slots no started game names are not touched.
+ * raz_league_turn: the engines' present descriptors are compared with the uploaded copies (host memcmp) and uploaded again, ordered on
+ *   `stream`, where they differ; then one launch over all games under raz_match_turn's rule, with (model, slot) read from the game's
+ *   pairing and the engine from the table.  An engine error flag, phase done, an idle slot without exactly one ply, or a 65th ply ends
+ *   the game and ORs into the error word: a league never spins.
+ * raz_league_stats_sync: the counters (synchronises `stream`).  raz_league_read: the games, the pairings as kept, the log and the root
+ *   visit counts to host arrays of n_games, n_games, n_games x 64 and n_games x 64 x 64 entries (any may be NULL; synchronises).
+ * RAZ_EINVAL / RAZ_ESTATE with a message and NO launch: a NULL argument, n_models outside 2..16, n_games == 0, the same engine twice,
+ *   an engine not started, a workspace that is NULL, misaligned or short, a sims entry of 0, position arrays given in part or
+ *   misaligned, turn / read / stats before start. */
+typedef struct raz_league raz_league;
+#define RAZ_LEAGUE_MAX_MODELS 16
+#define RAZ_LEAGUE_MAX_PLIES RAZ_MATCH_MAX_PLIES
+typedef struct {
+    uint8_t black_model, white_model;   /* model indices: which engine plays black / white */
+    uint16_t pad0;
+    uint32_t black_slot, white_slot;    /* the slot of black_model's / white_model's engine that plays this game */
+    uint32_t pad1;
+} raz_league_pairing;            /* 16 bytes */
+typedef struct {
+    uint64_t black, white;       /* the real board, absolute colours */
+    uint8_t player;              /* side to move: 1 black / 2 white */
+    uint8_t black_model, white_model;
+    uint8_t searching;           /* whose slot is searching: 0 nobody (ended, or not started), 1 black's model's, 2 white's model's */
+    uint8_t winner;              /* 0 running; 1 black / 2 white / 3 draw */
+    uint8_t blacks, whites;      /* disc counts when the game ended */
+    uint8_t n_plies;             /* entries of the game's log */
+    uint8_t flags;               /* 0x10 ended by an illegal move, 0x20 by a resignation (as raz_env_step) | RAZ_LEAGUE_GAME_NOT_STARTED */
+    uint8_t pad8[3];
+    uint32_t pad;
+} raz_league_game;               /* 32 bytes */
+#define RAZ_LEAGUE_GAME_NOT_STARTED 0x40u   /* the pairing was unsound, or a lower game index holds one of its slots */
+typedef struct {
+    uint8_t who;                 /* the model index that moved */
+    int8_t action;               /* 0..63, -1 = resigned */
+    uint8_t turn, pad;
+} raz_league_ply;                /* 4 bytes */
+typedef struct {
+    uint32_t live;               /* games still running */
+    uint32_t plies;              /* plies handed off since raz_league_start */
+    uint32_t error;              /* 0, or engine error flags of a slot (1 pool, 2 table, 4 records, 8 path) | RAZ_LEAGUE_ERR_* */
+    uint32_t n_models;
+    uint32_t searching[RAZ_LEAGUE_MAX_MODELS];   /* slots searching per model */
+    uint32_t pad[12];
+} raz_league_stats;              /* 128 bytes */
+#define RAZ_LEAGUE_ERR_SLOT 0x100u       /* a searching slot finished outside the one-move protocol (phase done, or idle without exactly one ply) */
+#define RAZ_LEAGUE_ERR_LOG_FULL 0x200u   /* a game's 65th ply */
+#define RAZ_LEAGUE_ERR_PAIRING 0x800u    /* raz_league_start left a game out (RAZ_LEAGUE_GAME_NOT_STARTED) */
+size_t raz_league_workspace_bytes(uint32_t n_models, const uint32_t* slots_per_model, uint32_t n_games);
+int raz_league_create(raz_engine* const* engines, uint32_t n_models, void* d_workspace, size_t workspace_bytes, uint32_t n_games,
+                      raz_league** out);
+void raz_league_destroy(raz_league* l);
+int raz_league_start(raz_league* l, const raz_league_pairing* d_pairings, const uint64_t* d_black, const uint64_t* d_white,
+                     const uint8_t* d_player, const uint32_t* sims_per_model, int enable_resign, raz_stream_t stream);
+int raz_league_turn(raz_league* l, raz_stream_t stream);
+int raz_league_stats_sync(raz_league* l, raz_league_stats* out, raz_stream_t stream);
+int raz_league_read(raz_league* l, raz_league_game* games, raz_league_pairing* pairings, raz_league_ply* log, uint32_t* log_root_n,
+                    raz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

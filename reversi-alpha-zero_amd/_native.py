@@ -101,6 +101,18 @@ class RazAnalysisStats(ctypes.Structure):
                 ("searched", c_uint32), ("solved", c_uint32), ("failed", c_uint32), ("error", c_uint32)]
 
 
+class RazLeaguePairing(ctypes.Structure):
+    _fields_ = [("black_model", c_uint8), ("white_model", c_uint8), ("pad0", ctypes.c_uint16), ("black_slot", c_uint32),
+                ("white_slot", c_uint32), ("pad1", c_uint32)]
+
+
+class RazLeagueStats(ctypes.Structure):
+    _fields_ = [("live", c_uint32), ("plies", c_uint32), ("error", c_uint32), ("n_models", c_uint32), ("searching", c_uint32 * 16),
+                ("pad", c_uint32 * 12)]
+
+
+assert ctypes.sizeof(RazLeaguePairing) == 16 and ctypes.sizeof(RazLeagueStats) == 128
+
 SIGNATURES.update({
     "raz_net_weight_bytes": (c_size_t, [c_int, c_int, c_int]),
     "raz_net_scratch_bytes": (c_size_t, [c_int, c_int, c_size_t]),
@@ -184,6 +196,14 @@ SIGNATURES.update({
     "raz_analysis_collect": (c_int, [c_void_p, c_void_p]),
     "raz_analysis_stats_sync": (c_int, [c_void_p, POINTER(RazAnalysisStats), c_void_p]),
     "raz_analysis_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # a league of up to 16 models on the device (csrc/raz_league.h); the handle travels as c_void_p, the engines as an array of them
+    "raz_league_workspace_bytes": (c_size_t, [c_uint32, POINTER(c_uint32), c_uint32]),
+    "raz_league_create": (c_int, [POINTER(c_void_p), c_uint32, c_void_p, c_size_t, c_uint32, POINTER(c_void_p)]),
+    "raz_league_destroy": (None, [c_void_p]),
+    "raz_league_start": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint32), c_int, c_void_p]),
+    "raz_league_turn": (c_int, [c_void_p, c_void_p]),
+    "raz_league_stats_sync": (c_int, [c_void_p, POINTER(RazLeagueStats), c_void_p]),
+    "raz_league_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1070,6 +1070,7 @@ extern "C" int raz_engine_set_positions(raz_engine* e, uint32_t first_slot, uint
 
 #include "raz_match.h"   // evaluation matches on the device: the hand-off between two engines (raz_match_*)
 #include "raz_analysis.h"   // retrograde analysis of whole games on the device: replay, arming and reduction (raz_analysis_*)
+#include "raz_league.h"   // a league of up to 16 models on the device: the hand-off with a pairing per game (raz_league_*)
 
 // Prune unreachable nodes (positions with fewer discs than the current real position) in every
 // game whose pool holds at least `threshold` nodes.  Asynchronous on `stream`; call between

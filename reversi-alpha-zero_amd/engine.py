@@ -727,6 +727,164 @@ class DeviceMatch:
         return match_games(*self.read(), first_game_id=first_game_id)
 
 
+LEAGUE_PAIRING = np.dtype([("black_model", "u1"), ("white_model", "u1"), ("pad0", "<u2"), ("black_slot", "<u4"), ("white_slot", "<u4"),
+                           ("pad1", "<u4")])
+LEAGUE_GAME = np.dtype([("black", "<u8"), ("white", "<u8"), ("player", "u1"), ("black_model", "u1"), ("white_model", "u1"),
+                        ("searching", "u1"), ("winner", "u1"), ("blacks", "u1"), ("whites", "u1"), ("n_plies", "u1"), ("flags", "u1"),
+                        ("pad8", "u1", (3,)), ("pad", "<u4")])
+LEAGUE_PLY = np.dtype([("who", "u1"), ("action", "i1"), ("turn", "u1"), ("pad", "u1")])
+LEAGUE_STATS = np.dtype([("live", "<u4"), ("plies", "<u4"), ("error", "<u4"), ("n_models", "<u4"), ("searching", "<u4", (16,)),
+                         ("pad", "<u4", (12,))])
+assert LEAGUE_PAIRING.itemsize == 16 and LEAGUE_GAME.itemsize == 32 and LEAGUE_PLY.itemsize == 4 and LEAGUE_STATS.itemsize == 128
+LEAGUE_MAX_MODELS, LEAGUE_MAX_PLIES = 16, MATCH_MAX_PLIES   # include/raz.h RAZ_LEAGUE_MAX_*
+LEAGUE_GAME_NOT_STARTED = 0x40
+LEAGUE_ERR_SLOT, LEAGUE_ERR_LOG_FULL, LEAGUE_ERR_PAIRING = 0x100, 0x200, 0x800
+
+
+def league_error_text(error):
+    return (f"league error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
+            f"0x100 a slot left the one-move protocol, 0x200 a game's log is full: the games it hit ended undecided; "
+            f"0x800 a pairing was unsound or lost its slot to a lower game index: the game was not started)")
+
+
+def league_pairings(pairings):
+    """LEAGUE_PAIRING records from (black_model, black_slot, white_model, white_slot) tuples."""
+    out = np.zeros(len(pairings), dtype=LEAGUE_PAIRING)
+    for g, (bm, bs, wm, ws) in enumerate(pairings):
+        out[g]["black_model"], out[g]["black_slot"], out[g]["white_model"], out[g]["white_slot"] = bm, bs, wm, ws
+    return out
+
+
+def league_results(games):
+    """Per game (winner model or None - a draw, undecided or not started -, black_model, white_model, (blacks, whites)) from the
+    LEAGUE_GAME records of a finished league."""
+    out = []
+    for r in games:
+        w, bm, wm = int(r["winner"]), int(r["black_model"]), int(r["white_model"])
+        out.append((bm if w == 1 else wm if w == 2 else None, bm, wm, (int(r["blacks"]), int(r["whites"]))))
+    return out
+
+
+def league_games(games, log, log_n, game_ids=None):
+    """The league ply by ply, in the shape of match_games with black_model / white_model and `who` a model index, from
+    raz_league_read's host arrays.  game_ids: per game (None: the game's index)."""
+    log, log_n = log.reshape(len(games), LEAGUE_MAX_PLIES), log_n.reshape(len(games), LEAGUE_MAX_PLIES, 64)
+    return [{"game_id": g if game_ids is None else game_ids[g], "black_model": int(r["black_model"]), "white_model": int(r["white_model"]),
+             "started": not int(r["flags"]) & LEAGUE_GAME_NOT_STARTED,
+             "plies": [{"who": int(log[g, i]["who"]), "action": int(log[g, i]["action"]), "root_n": log_n[g, i].copy()}
+                       for i in range(int(r["n_plies"]))]} for g, r in enumerate(games)]
+
+
+class DeviceLeague:
+    """A league of 2..16 started engines, one per model, on the device (include/raz.h raz_league_*): game g names its two models and the
+    slot of each model's engine that plays it.  The engines may differ in n_games.  The caller steps the engines; turn() hands every
+    decided move to the next mover's slot where it lies, without a host round trip."""
+
+    def __init__(self, engines, workspace=None):
+        """workspace: a uint8 device tensor of at least workspace_bytes(n_games) + 255 bytes to keep the league in (None: the league's
+        own, sized by every start)."""
+        self.engines = list(engines)
+        if not 2 <= len(self.engines) <= LEAGUE_MAX_MODELS:
+            raise ValueError(f"a league has 2..{LEAGUE_MAX_MODELS} engines, one per model")
+        if len({id(e) for e in self.engines}) != len(self.engines):
+            raise ValueError("every model of a league needs an engine of its own")
+        self.device = self.engines[0].device
+        self._given, self._ws, self._h = workspace, None, ctypes.c_void_p()
+        self.n_games = 0
+
+    def workspace_bytes(self, n_games):
+        slots = (ctypes.c_uint32 * len(self.engines))(*[e.n_games for e in self.engines])
+        return int(lib.raz_league_workspace_bytes(len(self.engines), slots, int(n_games)))
+
+    def _destroy(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib.raz_league_destroy(h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        self._destroy()
+
+    def start(self, pairings, positions=None, sims=None, enable_resign=True):
+        """pairings: uint8 device tensor [n_games, 16] of LEAGUE_PAIRING records (league_pairings).  positions: None (the initial
+        position, black to move) or (black int64, white int64, player uint8) device tensors [n_games], playable positions.
+        sims: simulations a move, one number or one per model."""
+        import torch
+        if not (isinstance(pairings, torch.Tensor) and pairings.is_cuda and pairings.is_contiguous() and pairings.dtype == torch.uint8
+                and pairings.numel() and pairings.numel() % LEAGUE_PAIRING.itemsize == 0):
+            raise ValueError("DeviceLeague.start takes the pairings as a contiguous uint8 device tensor [n_games, 16] (no CPU tensors)")
+        n = pairings.numel() // LEAGUE_PAIRING.itemsize
+        if positions is not None and len(positions) != 3:
+            raise ValueError("positions is (black, white, player)")
+        for t in positions or ():
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
+                raise ValueError("DeviceLeague.start takes contiguous device tensors of n_games entries (no CPU tensors)")
+        if positions is not None and (positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8):
+            raise ValueError("positions: int64, int64, uint8")
+        if not sims:
+            raise ValueError("sims: simulations a move, one number or one per model")
+        per_model = [int(sims)] * len(self.engines) if np.isscalar(sims) else [int(s) for s in sims]
+        if len(per_model) != len(self.engines):
+            raise ValueError("sims: one entry per model")
+        if n != self.n_games or not self._h:
+            self._destroy()
+            need = self.workspace_bytes(n)
+            ws = self._given if self._given is not None else torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
+            base = (ws.data_ptr() + 255) // 256 * 256
+            if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and need and base + need <= ws.data_ptr() + ws.numel()):
+                raise ValueError("workspace: a contiguous uint8 device tensor with workspace_bytes(n_games) behind its first 256-byte boundary")
+            handles = (ctypes.c_void_p * len(self.engines))(*[e._h.value for e in self.engines])
+            check(lib.raz_league_create(handles, len(self.engines), base, need, n, ctypes.byref(self._h)), "raz_league_create")
+            self._ws, self.workspace_base, self.n_games = ws, base, n
+        self._args = [pairings] + list(positions or ())   # (kept alive until the launches have run)
+        b, w, p = (t.data_ptr() for t in positions) if positions is not None else (None, None, None)
+        with torch.cuda.device(self.device):
+            check(lib.raz_league_start(self._h, pairings.data_ptr(), b, w, p, (ctypes.c_uint32 * len(per_model))(*per_model),
+                                       int(enable_resign), _stream()), "raz_league_start")
+
+    def _started(self, what):
+        if not self._h:
+            raise RuntimeError(f"DeviceLeague.{what}: call start first (raz_league_start)")
+
+    def turn(self):
+        import torch
+        self._started("turn")
+        with torch.cuda.device(self.device):
+            check(lib.raz_league_turn(self._h, _stream()), "raz_league_turn")
+
+    def stats(self, raise_on_error=True):
+        """{"live", "plies", "error", "n_models", "searching": [per model]}; raises on the league's error word.  Synchronises."""
+        import torch
+        self._started("stats")
+        st = N.RazLeagueStats()
+        with torch.cuda.device(self.device):
+            check(lib.raz_league_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_league_stats_sync")
+        if st.error and raise_on_error:
+            raise RuntimeError(league_error_text(st.error))
+        return {"live": st.live, "plies": st.plies, "error": st.error, "n_models": st.n_models,
+                "searching": [int(x) for x in st.searching[:len(self.engines)]]}
+
+    def read(self, log=True):
+        """(LEAGUE_GAME [n], LEAGUE_PAIRING [n], LEAGUE_PLY [n, 64] or None, root visit counts i32 [n, 64, 64] or None) on the host."""
+        import torch
+        self._started("read")
+        n = self.n_games
+        games, pairings = np.zeros(n, dtype=LEAGUE_GAME), np.zeros(n, dtype=LEAGUE_PAIRING)
+        plies = np.zeros((n, LEAGUE_MAX_PLIES), dtype=LEAGUE_PLY) if log else None
+        root_n = np.zeros((n, LEAGUE_MAX_PLIES, 64), dtype=np.int32) if log else None
+        with torch.cuda.device(self.device):
+            check(lib.raz_league_read(self._h, games.ctypes.data, pairings.ctypes.data, plies.ctypes.data if log else None,
+                                      root_n.ctypes.data if log else None, _stream()), "raz_league_read")
+        return games, pairings, plies, root_n
+
+    def results(self):
+        return league_results(self.read(log=False)[0])
+
+    def games(self, game_ids=None):
+        g, _, plies, root_n = self.read()
+        return league_games(g, plies, root_n, game_ids=game_ids)
+
+
 ANALYSIS_GAME = np.dtype([("positions", "<u4"), ("ended", "u1"), ("winner", "u1"), ("blacks", "u1"), ("whites", "u1"), ("errors", "<u4"),
                           ("searched", "<u4")])
 ANALYSIS_POS = np.dtype([("black", "<u8"), ("white", "<u8"), ("player", "u1"), ("state", "u1"), ("moves_made", "u1"), ("played", "i1"),

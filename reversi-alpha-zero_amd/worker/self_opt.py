@@ -12,6 +12,9 @@ the reference's own consumers.  One rank: world > 1 is refused.
 evaluate=True closes the reference's third process into the loop as well: after a training pass every model under next_generation/
 is challenged in this process by EvaluateWorker(handoff="device") - the match whose hand-offs stay on the device - and promoted or
 removed as the `eval` worker does it, so that the next block's digest check finds a new best model without a second process.
+
+archive_generations=True keeps what the `eval` worker throws away: every promoted challenger is also saved under
+<model_dir>/generations/, and the best model the run started from as generation 0, for worker/league.py to rate.
 """
 import os
 from logging import getLogger
@@ -23,11 +26,34 @@ def _world():
     return int(os.environ.get("WORLD_SIZE", "1"))
 
 
-def evaluate_challengers(config, evaluator, player=None):
+GENERATION_ZERO = "00000000-000000.000000"   # sorts before every challenger's time stamp
+
+
+def generations_dir(config):
+    return os.path.join(config.resource.model_dir, "generations")
+
+
+def archived_generation_dirs(config):
+    """The archived generations in name order: the starting model first, then the promotions by their challengers' time stamps."""
+    from glob import glob
+    return sorted(glob(os.path.join(generations_dir(config), config.resource.next_generation_model_dirname_tmpl % "*")))
+
+
+def archive_generation(config, model, dirname):
+    """Save `model` as <model_dir>/generations/<dirname>/ under the next-generation file names.  Returns the directory."""
+    rc = config.resource
+    d = os.path.join(generations_dir(config), dirname)
+    os.makedirs(d, exist_ok=True)
+    model.save(os.path.join(d, rc.next_generation_model_config_filename), os.path.join(d, rc.next_generation_model_weight_filename))
+    return d
+
+
+def evaluate_challengers(config, evaluator, player=None, archive=False):
     """Challenge every model under next_generation/ (evaluate.py:31-42 without the polling sleep: the directory is listed, never waited
     for) with `evaluator`, an EvaluateWorker: the better one becomes the best model, every one is removed.  The two engines of a
     challenge live for that challenge only; where they do not fit beside `player`'s self-play engine, that engine is dropped first
-    (BatchedSelfPlayWorker._drop_engine: the next block rebuilds it).  Returns [(model_dir, became_best)]."""
+    (BatchedSelfPlayWorker._drop_engine: the next block rebuilds it).  archive: a promoted challenger is also saved under generations/,
+    in a directory of its own directory's name.  Returns [(model_dir, became_best)]."""
     import gc
     import torch
     from ..lib.data_helper import get_next_generation_model_dirs
@@ -52,6 +78,8 @@ def evaluate_challengers(config, evaluator, player=None):
         if better:
             save_as_best_model(ng_model)
             evaluator.best_model = ng_model
+            if archive:
+                archive_generation(config, ng_model, os.path.basename(os.path.normpath(model_dir)))
         evaluator.remove_model(model_dir)
         decisions.append((model_dir, better))
         gc.collect()
@@ -60,10 +88,12 @@ def evaluate_challengers(config, evaluator, player=None):
 
 
 def start(config, games_in_flight=None, backend="hip", precision=None, write_files=False, total_blocks=None, seed=0, block_games=None,
-          evaluate=False):
+          evaluate=False, archive_generations=False):
     """Alternate play - store - train until total_blocks blocks have been played (None = forever).  Returns (the self-play worker, the
     optimize worker, the replay).  block_games: the game ids of a block (default: the `self` worker's default_block_games, rounded up to
-    whole play files).  evaluate: challenge the models a training pass saved, in this process (evaluate_challengers)."""
+    whole play files).  evaluate: challenge the models a training pass saved, in this process (evaluate_challengers).
+    archive_generations: with evaluate, keep every promoted model, and the best model of the first block, under <model_dir>/generations/
+    (False: nothing is written there)."""
     if _world() > 1:
         raise ValueError(f"self_opt runs one process on one GPU (WORLD_SIZE={_world()}): run the `self` and `opt` workers for more")
     import torch
@@ -114,7 +144,9 @@ def start(config, games_in_flight=None, backend="hip", precision=None, write_fil
             if evaluator is None:
                 from .evaluate import EvaluateWorker
                 evaluator = EvaluateWorker(config, seed=seed, device=device, handoff="device")
-            evaluate_challengers(config, evaluator, player)
+                if archive_generations and not os.path.isdir(os.path.join(generations_dir(config), rc.next_generation_model_dirname_tmpl % GENERATION_ZERO)):
+                    archive_generation(config, evaluator.load_best_model(), rc.next_generation_model_dirname_tmpl % GENERATION_ZERO)
+            evaluate_challengers(config, evaluator, player, archive=archive_generations)
         new_blob = model.model.to_blob() if try_reload_model(config, model) else None
         if new_blob is not None:
             player.set_net_blob(new_blob)
