@@ -639,7 +639,7 @@ int raz_train_rows_fill(const void* d_headers, const uint32_t* d_root_n, const r
                         const uint32_t* d_row_offset, uint64_t capacity_rows, uint64_t* d_own, uint64_t* d_enemy, float* d_policy,
                         int8_t* d_z, raz_stream_t stream);
 
-/* ---- evaluation matches on the device: the hand-off between two engines (csrc/raz_match.h) -----------------------
+/* ---- evaluation matches on the device: the hand-off between two engines (csrc/raz_match.h, raz_handoff.h) --------
  * The reference's evaluator (worker/evaluate.py:66-96) plays best model against challenger with two ReversiPlayer objects and one
  * ReversiEnv per game.  A match couples two STARTED engines of the same n_games - slot g of each is that model's player in game g,
  * with the tree, random streams and one-move semantics raz_engine_set_position gives it - and keeps every game's env in a

@@ -10,8 +10,8 @@
 // Entries after the game is over are IGNORED: the reference would go on calling env.step on a finished env (moving discs of a game
 // that has a winner); that is not reproduced.
 //
-// Part of raz_engine.hip's translation unit (it needs struct raz_engine and arm_slot); board logic is raz_bitboard.h's, the wave
-// reductions are raz_engine_core.h's.  Plain vector stores, no scratch, integer atomics for the counters of the stats block only.
+// Part of raz_engine.hip's translation unit, behind raz_handoff.h (the decided-slot rule, the carve, the host checks); board logic is
+// raz_bitboard.h's, the wave reductions are raz_engine_core.h's.  Plain vector stores, no scratch, atomics for the stats block only.
 #pragma once
 
 namespace {
@@ -29,26 +29,20 @@ struct raz_analysis_dev {
 static_assert(sizeof(raz_analysis_stats) == 32 && sizeof(raz_analysis_game) == 16 && sizeof(raz_analysis_pos) == 24 &&
                   sizeof(raz_analysis_eval) == 128, "raz_analysis layouts");
 
-// Carve the workspace; with base == nullptr only the total size is computed.
 inline size_t analysis_carve(uint32_t n, uint32_t max_moves, uint32_t first_slot, unsigned char* base, raz_analysis_dev* A) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> unsigned char* {
-        unsigned char* p = base ? base + off : nullptr;
-        off = match_up(off + bytes);
-        return p;
-    };
+    carver ws{base, 0};
     raz_analysis_dev d;
     d.n = n;
     d.max_moves = max_moves;
     d.P = max_moves + 1;
     d.first_slot = first_slot;
     const size_t np = (size_t)n * d.P;
-    d.counters = (uint32_t*)take(sizeof(raz_analysis_stats));
-    d.game = (raz_analysis_game*)take((size_t)n * sizeof(raz_analysis_game));
-    d.pos = (raz_analysis_pos*)take(np * sizeof(raz_analysis_pos));
-    d.eval = (raz_analysis_eval*)take(np * sizeof(raz_analysis_eval));
+    d.counters = (uint32_t*)ws.take(sizeof(raz_analysis_stats));
+    d.game = (raz_analysis_game*)ws.take((size_t)n * sizeof(raz_analysis_game));
+    d.pos = (raz_analysis_pos*)ws.take(np * sizeof(raz_analysis_pos));
+    d.eval = (raz_analysis_eval*)ws.take(np * sizeof(raz_analysis_eval));
     if (A) *A = d;
-    return off;
+    return ws.off;
 }
 
 // The replay.  Thread g walks game g's list as NBoardEngine.set_game does, writes the position before every entry and arms the slot of
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(256) void k_analysis_start(raz_analysis_dev A, raz_
 }
 
 // The reduction.  One wave per position, lane = square.  Where the position is pending and its slot has decided (phase idle, one ply
-// recorded: k_match_turn's rule), the root's statistics become the position's eval; a position already collected, not searched, or
+// recorded: raz_handoff.h slot_answer), the root's statistics become the position's eval; a position already collected, not searched, or
 // still searching is left alone, byte for byte.
 __global__ __launch_bounds__(64 * kAnaWavesPerBlock) void k_analysis_collect(raz_analysis_dev A, raz_engine_dev E) {
     const int lane = (int)(threadIdx.x & 63u);
@@ -125,13 +119,8 @@ __global__ __launch_bounds__(64 * kAnaWavesPerBlock) void k_analysis_collect(raz
     raz_analysis_eval* ev = A.eval + pi;
     if (ev->state != RAZ_ANALYSIS_EVAL_PENDING) return;
     const uint32_t slot = A.first_slot + (uint32_t)pi;
-    const raz_game& G = E.game[slot];
-    const uint32_t phase = G.phase, slot_plies = G.n_plies;
-    uint32_t err = G.error;
-    if (!err) {
-        if (phase != RAZ_PHASE_IDLE && phase != RAZ_PHASE_DONE) return;   // still searching: no position waits for another
-        if (phase == RAZ_PHASE_DONE || slot_plies != 1u) err = RAZ_ANALYSIS_ERR_SLOT;
-    }
+    const uint32_t err = slot_answer(E.game[slot]);
+    if (err == kSlotSearching) return;   // no position waits for another
     const int played = A.pos[pi].played;
     if (err) {
         if (lane == 0) {
@@ -229,9 +218,8 @@ extern "C" int raz_analysis_create(raz_engine* engine, uint32_t first_slot, void
     if (!engine->dev.rec_w) return raz_fail(RAZ_ESTATE, "raz_analysis_create: engine created with record_root_w=0");
     if ((unsigned long long)first_slot + (unsigned long long)n_games * (max_moves + 1) > engine->dev.B)
         return raz_fail(RAZ_EINVAL, "raz_analysis_create: first_slot + n_games x (max_moves + 1) is beyond the engine's slots");
-    if ((uintptr_t)d_workspace % 256) return raz_fail(RAZ_EINVAL, "raz_analysis_create: workspace must be 256-byte aligned");
     const size_t need = analysis_carve(n_games, max_moves, first_slot, nullptr, nullptr);
-    if (workspace_bytes < need) return raz_fail(RAZ_EINVAL, "raz_analysis_create: workspace smaller than raz_analysis_workspace_bytes()");
+    if (int rc = handoff_check_workspace("raz_analysis_create", "raz_analysis_workspace_bytes()", d_workspace, workspace_bytes, need)) return rc;
     raz_analysis* a = new (std::nothrow) raz_analysis();
     if (!a) return raz_fail(RAZ_ENOMEM, "raz_analysis_create: out of host memory");
     a->engine = engine;
@@ -247,9 +235,7 @@ extern "C" void raz_analysis_destroy(raz_analysis* a) { delete a; }
 extern "C" int raz_analysis_start(raz_analysis* a, const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player,
                                   const int8_t* d_moves, uint32_t sims, raz_stream_t stream) {
     if (!a || !d_moves) return raz_fail(RAZ_EINVAL, "raz_analysis_start: NULL argument");
-    if ((d_black != nullptr) != (d_white != nullptr) || (d_black != nullptr) != (d_player != nullptr))
-        return raz_fail(RAZ_EINVAL, "raz_analysis_start: d_black, d_white and d_player go together, all or none");
-    if ((uintptr_t)d_black % 8 || (uintptr_t)d_white % 8) return raz_fail(RAZ_EINVAL, "raz_analysis_start: d_black / d_white must be 8-byte aligned");
+    if (int rc = handoff_check_positions("raz_analysis_start", d_black, d_white, d_player)) return rc;
     if (sims == 0) return raz_fail(RAZ_EINVAL, "raz_analysis_start: sims must be > 0");
     if (!a->engine->started) return raz_fail(RAZ_ESTATE, "raz_analysis_start: the engine is not started");
     hipStream_t s = (hipStream_t)stream;

@@ -909,7 +909,7 @@ extern "C" int raz_engine_stats_sync(raz_engine* e, raz_engine_stats* out, raz_s
 namespace {
 // Arming a slot, stated once: put slot g on (black, white, `player` to move) and ask for a move of `sims` simulations, keeping the
 // slot's tree, random-stream counters and - unless one_move - its records.  One thread per slot; called by k_set_position,
-// k_set_positions and the match kernels (raz_match.h).
+// k_set_positions, the hand-off (raz_handoff.h) and the analysis (raz_analysis.h).
 __device__ __forceinline__ void arm_slot(const raz_engine_dev& E, uint32_t g, unsigned long long black, unsigned long long white,
                                          uint32_t player, uint32_t sims, uint32_t enable_resign, uint32_t one_move) {
     raz_game& G = E.game[g];
@@ -1068,6 +1068,7 @@ extern "C" int raz_engine_set_positions(raz_engine* e, uint32_t first_slot, uint
     return raz_check_launch("raz_engine_set_positions");
 }
 
+#include "raz_handoff.h"   // the one-move hand-off the three below rest on: the decided-slot rule, seats, the start and turn bodies
 #include "raz_match.h"   // evaluation matches on the device: the hand-off between two engines (raz_match_*)
 #include "raz_analysis.h"   // retrograde analysis of whole games on the device: replay, arming and reduction (raz_analysis_*)
 #include "raz_league.h"   // a league of up to 16 models on the device: the hand-off with a pairing per game (raz_league_*)

@@ -1,15 +1,13 @@
-// raz_league.h — a league of up to 16 models on the device: the hand-off of raz_match.h with (model, slot) read from a pairing per
+// raz_league.h — a league of up to 16 models on the device: the hand-off of raz_handoff.h with (model, slot) read from a pairing per
 // game instead of "two engines, slot g <-> game g" (include/raz.h raz_league_*).
 //
-// Game g names its two models and the slot of each model's engine that plays it (raz_league_pairing).  The slot protocol is the
-// match's: a slot in one-move mode leaves, after its search, the position after the move IN THE MOVER'S FRAME, the status in that
-// frame and the ply's record 0; k_league_turn reads that, keeps the game's real board in absolute colours and arms the next
-// mover's slot in that mover's engine.  The engines' descriptors (raz_engine_dev) are a TABLE IN THE WORKSPACE, not kernel
-// arguments: sixteen of them do not fit a kernel-argument segment (static_assert below).
+// Game g names its two models and the slot of each model's engine that plays it (raz_league_pairing); league_ctx makes seats of
+// them, and start_game / turn_game (raz_handoff.h) do the rest as they do it for the match.  The engines' descriptors
+// (raz_engine_dev) are a TABLE IN THE WORKSPACE, not kernel arguments: sixteen of them do not fit a kernel-argument segment
+// (static_assert below).
 //
-// Part of raz_engine.hip's translation unit (it needs struct raz_engine and arm_slot); board logic is raz_bitboard.h's.
-// One thread per game; plain vector stores, no floating point, integer atomics for the counters and the claim words only.
-// k_match_turn's text is NOT shared with k_league_turn: raz_match.h is left as it is.
+// Part of raz_engine.hip's translation unit, behind raz_handoff.h.  One thread per game; plain vector stores, no floating point,
+// integer atomics for the counters and the claim words only.
 #pragma once
 
 namespace {
@@ -32,19 +30,12 @@ struct raz_league_dev {
 };
 static_assert(sizeof(raz_league_pairing) == 16 && sizeof(raz_league_game) == 32 && sizeof(raz_league_ply) == 4 &&
               sizeof(raz_league_stats) == 128, "raz_league layouts");
-static_assert(RAZ_LEAGUE_MAX_PLIES == RAZ_MATCH_MAX_PLIES, "a league game's log is a match game's");
 static_assert(RAZ_LEAGUE_MAX_MODELS * sizeof(raz_engine_dev) > 4096, "the descriptor table would fit kernel arguments: it need not live in HBM");
 static_assert(sizeof(raz_engine_dev) % 8 == 0, "raz_engine_dev [n_models] in a 256-byte aligned section");
 
-// Carve the workspace; with base == nullptr only the total size is computed.  The sections raz_league_start clears (counters, games,
-// log headers; claim words) lie together.
+// The sections raz_league_start clears (counters, games, log headers; claim words) lie together.
 inline size_t league_carve(uint32_t n_models, const uint32_t* slots, uint32_t n_games, unsigned char* base, raz_league_dev* L) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> unsigned char* {
-        unsigned char* p = base ? base + off : nullptr;
-        off = match_up(off + bytes);
-        return p;
-    };
+    carver ws{base, 0};
     raz_league_dev d;
     memset(&d, 0, sizeof d);
     d.n_games = n_games;
@@ -55,16 +46,16 @@ inline size_t league_carve(uint32_t n_models, const uint32_t* slots, uint32_t n_
         d.slots[m] = slots[m];
         total += slots[m];
     }
-    d.counters = (uint32_t*)take(sizeof(raz_league_stats) + RAZ_LEAGUE_MAX_MODELS * 4);
+    d.counters = (uint32_t*)ws.take(sizeof(raz_league_stats) + RAZ_LEAGUE_MAX_MODELS * 4);
     d.sims = base ? d.counters + sizeof(raz_league_stats) / 4 : nullptr;
-    d.table = (raz_engine_dev*)take((size_t)n_models * sizeof(raz_engine_dev));
-    d.pairing = (raz_league_pairing*)take((size_t)n_games * sizeof(raz_league_pairing));
-    d.game = (raz_league_game*)take((size_t)n_games * sizeof(raz_league_game));
-    d.log = (raz_league_ply*)take((size_t)n_games * RAZ_LEAGUE_MAX_PLIES * sizeof(raz_league_ply));
-    d.claim = (uint32_t*)take(total * 4);
-    d.log_n = (uint32_t*)take((size_t)n_games * RAZ_LEAGUE_MAX_PLIES * 64 * 4);
+    d.table = (raz_engine_dev*)ws.take((size_t)n_models * sizeof(raz_engine_dev));
+    d.pairing = (raz_league_pairing*)ws.take((size_t)n_games * sizeof(raz_league_pairing));
+    d.game = (raz_league_game*)ws.take((size_t)n_games * sizeof(raz_league_game));
+    d.log = (raz_league_ply*)ws.take((size_t)n_games * RAZ_LEAGUE_MAX_PLIES * sizeof(raz_league_ply));
+    d.claim = (uint32_t*)ws.take(total * 4);
+    d.log_n = (uint32_t*)ws.take((size_t)n_games * RAZ_LEAGUE_MAX_PLIES * 64 * 4);
     if (L) *L = d;
-    return off;
+    return ws.off;
 }
 
 // Both model indices below n_models and different, both slots below their engine's n_games.
@@ -81,14 +72,19 @@ __device__ __forceinline__ void league_claim(uint32_t* word, uint32_t g) {
 #endif
 }
 
-// Ask the model that plays colour `player` in game (mg, P) for its move on the real board: the mover's own discs are "black" inside
-// its tree, whatever its colour in the game (agent/player.py:95), so the slot is armed with player 1.
-__device__ __forceinline__ void league_arm(const raz_league_dev& L, const raz_league_game& mg, const raz_league_pairing& P,
-                                           uint32_t enable_resign) {
-    const bool b = mg.player == RAZ_PLAYER_BLACK;
-    const uint32_t model = b ? P.black_model : P.white_model, slot = b ? P.black_slot : P.white_slot;
-    arm_slot(L.table[model], slot, b ? mg.black : mg.white, b ? mg.white : mg.black, RAZ_PLAYER_BLACK, L.sims[model], enable_resign, 1u);
-}
+// The league's seats: (model, slot) of a colour from the game's pairing, the engine from the table in the workspace.
+struct league_ctx {
+    const raz_league_dev& D;
+    const raz_league_pairing P;
+    uint32_t enable_resign;
+    enum { live = kLeagueLive, plies = kLeaguePlies, error = kLeagueError, searching = kLeagueSearching };
+    __device__ __forceinline__ handoff_seat seat(uint32_t, const raz_league_game&, uint32_t colour) const {
+        const bool b = colour == RAZ_PLAYER_BLACK;
+        const uint32_t model = b ? P.black_model : P.white_model;
+        return handoff_seat{D.table[model], b ? P.black_slot : P.white_slot, model, D.sims[model]};
+    }
+    __device__ __forceinline__ uint32_t code(const raz_league_game&, uint32_t colour) const { return colour; }   // 1: black's model's slot, 2: white's
+};
 
 // Start, first launch: keep game g's pairing and, where it is sound, claim its two slots for the lowest game index that names them.
 // (The claim words were set to 0xffffffff by the memset ahead of this launch.)
@@ -104,8 +100,8 @@ __global__ __launch_bounds__(256) void k_league_claim(raz_league_dev L, const ra
     league_claim(&L.claim[L.claim_off[P.white_model] + P.white_slot], g);
 }
 
-// Start, second launch: game g starts where its pairing is sound and both its slots are its own; then as k_match_start starts one.
-// Slots no started game names are not touched.
+// Start, second launch: game g starts where its pairing is sound and both its slots are its own; then as k_match_start starts one
+// (start_game).  Slots no started game names are not touched.
 __global__ __launch_bounds__(256) void k_league_start(raz_league_dev L, const unsigned long long* black, const unsigned long long* white,
                                                       const uint8_t* player, uint32_t enable_resign) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -113,12 +109,9 @@ __global__ __launch_bounds__(256) void k_league_start(raz_league_dev L, const un
     if (g == 0) L.counters[kLeagueModels] = L.n_models;
     const raz_league_pairing P = L.pairing[g];
     raz_league_game mg;
-    mg.black = black ? black[g] : RAZ_INIT_BLACK;
-    mg.white = black ? white[g] : RAZ_INIT_WHITE;
-    mg.player = black ? player[g] : (uint8_t)RAZ_PLAYER_BLACK;
+    init_game(mg, g, black, white, player);
     mg.black_model = P.black_model;
     mg.white_model = P.white_model;
-    mg.winner = mg.blacks = mg.whites = mg.n_plies = mg.flags = 0;
     mg.pad8[0] = mg.pad8[1] = mg.pad8[2] = 0;
     mg.pad = 0;
     const bool mine = league_sound(L, P) && L.claim[L.claim_off[P.black_model] + P.black_slot] == g &&
@@ -130,14 +123,10 @@ __global__ __launch_bounds__(256) void k_league_start(raz_league_dev L, const un
         atomicOr(&L.counters[kLeagueError], RAZ_LEAGUE_ERR_PAIRING);
         return;
     }
-    mg.searching = mg.player;   // 1: black's model's slot, 2: white's
-    L.game[g] = mg;
-    league_arm(L, mg, P, enable_resign);
-    atomicAdd(&L.counters[kLeagueLive], 1u);
-    atomicAdd(&L.counters[kLeagueSearching + (mg.player == RAZ_PLAYER_BLACK ? P.black_model : P.white_model)], 1u);
+    start_game(league_ctx{L, P, enable_resign}, g, mg);
 }
 
-// The hand-off: k_match_turn's rule with (model, slot) from the game's pairing and the engine from the table.
+// The hand-off (raz_handoff.h turn_game) for every game that is live, with (model, slot) from the game's pairing.
 __global__ __launch_bounds__(256) void k_league_turn(raz_league_dev L, uint32_t enable_resign) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= L.n_games) return;
@@ -145,64 +134,7 @@ __global__ __launch_bounds__(256) void k_league_turn(raz_league_dev L, uint32_t 
     if (mg.searching == 0) return;   // the game has ended, or never started
     mg.pad8[0] = mg.pad8[1] = mg.pad8[2] = 0;   // (stated, not carried: seven odd bytes carried from load to store cost a private array)
     mg.pad = 0;
-    const raz_league_pairing P = L.pairing[g];
-    const uint32_t model = mg.searching == 1 ? P.black_model : P.white_model, slot = mg.searching == 1 ? P.black_slot : P.white_slot;
-    const raz_engine_dev& E = L.table[model];
-    const raz_game& G = E.game[slot];
-    const uint32_t phase = G.phase, slot_error = G.error, slot_plies = G.n_plies;
-    uint32_t err = slot_error;
-    if (!err) {
-        if (phase != RAZ_PHASE_IDLE && phase != RAZ_PHASE_DONE) return;   // still searching: no game waits for another
-        if (phase == RAZ_PHASE_DONE || slot_plies != 1u) err = RAZ_LEAGUE_ERR_SLOT;
-        else if (mg.n_plies >= RAZ_LEAGUE_MAX_PLIES) err = RAZ_LEAGUE_ERR_LOG_FULL;
-    }
-    if (err) {   // the game ends here, undecided, and the league says why
-        atomicOr(&L.counters[kLeagueError], err);
-        atomicSub(&L.counters[kLeagueLive], 1u);
-        atomicSub(&L.counters[kLeagueSearching + model], 1u);
-        mg.searching = 0;
-        L.game[g] = mg;
-        return;
-    }
-    // the ply: the slot's record 0 (one-move mode records every move there)
-    const size_t ri = (size_t)slot * E.max_plies, li = (size_t)g * RAZ_LEAGUE_MAX_PLIES + mg.n_plies;
-    raz_league_ply ply;
-    ply.who = (uint8_t)model;
-    ply.action = E.rec[ri].action;
-    ply.turn = E.rec[ri].turn;
-    ply.pad = 0;
-    L.log[li] = ply;
-    const raz_match_q4* src = (const raz_match_q4*)(E.rec_n + ri * 64);
-    raz_match_q4* dst = (raz_match_q4*)(L.log_n + li * 64);
-    for (int i = 0; i < 16; ++i) dst[i] = src[i];
-    mg.n_plies += 1;
-    atomicAdd(&L.counters[kLeaguePlies], 1u);
-    // the slot's board and status, from the mover's frame ("black" = the mover) to absolute colours
-    const uint32_t mover = mg.player, other = 3u - mover;
-    const unsigned long long sb = G.root_black, sw = G.root_white;
-    const uint32_t status = G.status;
-    mg.black = mover == RAZ_PLAYER_BLACK ? sb : sw;
-    mg.white = mover == RAZ_PLAYER_BLACK ? sw : sb;
-    mg.player = (uint8_t)(G.player == RAZ_PLAYER_BLACK ? mover : other);
-    if (status) {
-        const uint32_t w = status & RAZ_STATUS_WINNER_MASK;
-        mg.winner = (uint8_t)(w == RAZ_WIN_BLACK ? mover : (w == RAZ_WIN_WHITE ? other : w));
-        mg.flags = (uint8_t)(status & ~(uint32_t)RAZ_STATUS_WINNER_MASK);
-        mg.blacks = (uint8_t)bb_popcount(mg.black);
-        mg.whites = (uint8_t)bb_popcount(mg.white);
-        mg.searching = 0;
-        atomicSub(&L.counters[kLeagueLive], 1u);
-        atomicSub(&L.counters[kLeagueSearching + model], 1u);
-    } else {
-        league_arm(L, mg, P, enable_resign);   // after a pass the same slot again
-        if (mg.player != mover) {
-            const uint32_t next = mg.player == RAZ_PLAYER_BLACK ? P.black_model : P.white_model;
-            mg.searching = mg.player;
-            atomicSub(&L.counters[kLeagueSearching + model], 1u);
-            atomicAdd(&L.counters[kLeagueSearching + next], 1u);
-        }
-    }
-    L.game[g] = mg;
+    turn_game(league_ctx{L, L.pairing[g], enable_resign}, g, mg);
 }
 
 }  // namespace
@@ -242,9 +174,8 @@ extern "C" int raz_league_create(raz_engine* const* engines, uint32_t n_models, 
     }
     for (uint32_t m = 0; m < n_models; ++m)
         if (!engines[m]->started) return raz_fail(RAZ_ESTATE, "raz_league_create: call raz_engine_start on every engine first");
-    if ((uintptr_t)d_workspace % 256) return raz_fail(RAZ_EINVAL, "raz_league_create: workspace must be 256-byte aligned");
-    if (workspace_bytes < league_carve(n_models, slots, n_games, nullptr, nullptr))
-        return raz_fail(RAZ_EINVAL, "raz_league_create: workspace smaller than raz_league_workspace_bytes()");
+    const size_t need = league_carve(n_models, slots, n_games, nullptr, nullptr);
+    if (int rc = handoff_check_workspace("raz_league_create", "raz_league_workspace_bytes()", d_workspace, workspace_bytes, need)) return rc;
     raz_league* l = new (std::nothrow) raz_league();
     if (!l) return raz_fail(RAZ_ENOMEM, "raz_league_create: out of host memory");
     for (uint32_t m = 0; m < n_models; ++m) l->engine[m] = engines[m];
@@ -271,9 +202,7 @@ int league_upload(raz_league* l, bool all, hipStream_t s, const char* what) {
 extern "C" int raz_league_start(raz_league* l, const raz_league_pairing* d_pairings, const uint64_t* d_black, const uint64_t* d_white,
                                 const uint8_t* d_player, const uint32_t* sims_per_model, int enable_resign, raz_stream_t stream) {
     if (!l || !d_pairings || !sims_per_model) return raz_fail(RAZ_EINVAL, "raz_league_start: NULL argument");
-    if ((d_black != nullptr) != (d_white != nullptr) || (d_black != nullptr) != (d_player != nullptr))
-        return raz_fail(RAZ_EINVAL, "raz_league_start: d_black, d_white and d_player go together, all or none");
-    if ((uintptr_t)d_black % 8 || (uintptr_t)d_white % 8) return raz_fail(RAZ_EINVAL, "raz_league_start: d_black / d_white must be 8-byte aligned");
+    if (int rc = handoff_check_positions("raz_league_start", d_black, d_white, d_player)) return rc;
     if ((uintptr_t)d_pairings % 4) return raz_fail(RAZ_EINVAL, "raz_league_start: d_pairings must be 4-byte aligned");
     raz_league_dev& d = l->dev;
     for (uint32_t m = 0; m < d.n_models; ++m) {
@@ -327,9 +256,7 @@ extern "C" int raz_league_read(raz_league* l, raz_league_game* games, raz_league
     const size_t n = d.n_games;
     if (games) RAZ_HIP_TRY(hipMemcpyAsync(games, d.game, n * sizeof(raz_league_game), hipMemcpyDeviceToHost, s), "raz_league_read: games");
     if (pairings) RAZ_HIP_TRY(hipMemcpyAsync(pairings, d.pairing, n * sizeof(raz_league_pairing), hipMemcpyDeviceToHost, s), "raz_league_read: pairings");
-    if (log) RAZ_HIP_TRY(hipMemcpyAsync(log, d.log, n * RAZ_LEAGUE_MAX_PLIES * sizeof(raz_league_ply), hipMemcpyDeviceToHost, s), "raz_league_read: log");
-    if (log_root_n)
-        RAZ_HIP_TRY(hipMemcpyAsync(log_root_n, d.log_n, n * RAZ_LEAGUE_MAX_PLIES * 64 * 4, hipMemcpyDeviceToHost, s), "raz_league_read: visit counts");
+    if (int rc = handoff_read_log("raz_league_read", n, log, d.log, log_root_n, d.log_n, s)) return rc;
     RAZ_HIP_TRY(hipStreamSynchronize(s), "raz_league_read: sync");
     return RAZ_OK;
 }

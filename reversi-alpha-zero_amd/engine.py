@@ -619,9 +619,54 @@ assert MATCH_GAME.itemsize == 32 and MATCH_PLY.itemsize == 4
 MATCH_MAX_PLIES = 64   # include/raz.h RAZ_MATCH_MAX_PLIES
 
 
+# ---- what DeviceMatch, DeviceLeague and DeviceAnalysis share: the engine hand-off of csrc/raz_handoff.h seen from the host ----------
+def _error_text(what, error, rest):
+    return (f"{what} error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
+            f"0x100 a slot left the one-move protocol, {rest}")
+
+
+def _workspace(given, need, device, what="workspace_bytes"):
+    """(tensor, base address): `given`, or the caller's own where it is None, with `need` bytes behind its first 256-byte boundary."""
+    import torch
+    ws = given if given is not None else torch.zeros(need + 256, dtype=torch.uint8, device=device)
+    base = (ws.data_ptr() + 255) // 256 * 256
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and need and base + need <= ws.data_ptr() + ws.numel()):
+        raise ValueError(f"workspace: a contiguous uint8 device tensor with {what} behind its first 256-byte boundary")
+    return ws, base
+
+
+def _positions(who, positions, n, leading=(), dtypes="positions: int64, int64, uint8"):
+    """The (black, white, player) pointers raz_*_start takes, three None for positions None; `leading` tensors are held to n entries too."""
+    import torch
+    if positions is not None and len(positions) != 3:
+        raise ValueError("positions is (black, white, player)")
+    for t in list(leading) + list(positions or ()):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
+            raise ValueError(f"{who}.start takes contiguous device tensors of n_games entries (no CPU tensors)")
+    if positions is None:
+        return None, None, None
+    if positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8:
+        raise ValueError(dtypes)
+    return tuple(t.data_ptr() for t in positions)
+
+
+def _log_arrays(n, log):
+    """Host arrays for a log of n games and their addresses: (MATCH_PLY [n, 64], visit counts i32 [n, 64, 64]), or None where not log."""
+    if not log:
+        return None, None, None, None
+    plies, root_n = np.zeros((n, MATCH_MAX_PLIES), dtype=MATCH_PLY), np.zeros((n, MATCH_MAX_PLIES, 64), dtype=np.int32)
+    return plies, root_n, plies.ctypes.data, root_n.ctypes.data
+
+
+def _ply_lists(games, log, log_n, who=int):
+    """Per game its plies as dictionaries, from raz_*_read's host arrays."""
+    log, log_n = log.reshape(len(games), MATCH_MAX_PLIES), log_n.reshape(len(games), MATCH_MAX_PLIES, 64)
+    return [[{"who": who(log[g, i]["who"]), "action": int(log[g, i]["action"]), "root_n": log_n[g, i].copy()} for i in range(int(r["n_plies"]))]
+            for g, r in enumerate(games)]
+
+
 def match_error_text(error):
-    return (f"match error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
-            f"0x100 a slot left the one-move protocol, 0x200 a game's log is full): the games it hit ended undecided")
+    return _error_text("match", error, "0x200 a game's log is full): the games it hit ended undecided")
 
 
 def match_results(games):
@@ -636,10 +681,8 @@ def match_results(games):
 
 def match_games(games, log, log_n, first_game_id=0):
     """The match ply by ply, in the dictionaries of EvaluateWorker.last_games, from raz_match_read's host arrays."""
-    log, log_n = log.reshape(len(games), MATCH_MAX_PLIES), log_n.reshape(len(games), MATCH_MAX_PLIES, 64)
-    return [{"game_id": first_game_id + g, "best_is_black": bool(r["best_is_black"]),
-             "plies": [{"who": "ng" if log[g, i]["who"] else "best", "action": int(log[g, i]["action"]), "root_n": log_n[g, i].copy()}
-                       for i in range(int(r["n_plies"]))]} for g, r in enumerate(games)]
+    plies = _ply_lists(games, log, log_n, who=lambda side: "ng" if side else "best")
+    return [{"game_id": first_game_id + g, "best_is_black": bool(r["best_is_black"]), "plies": plies[g]} for g, r in enumerate(games)]
 
 
 class DeviceMatch:
@@ -649,21 +692,14 @@ class DeviceMatch:
 
     def __init__(self, best_engine, challenger_engine, workspace=None):
         """workspace: a uint8 device tensor of at least workspace_bytes + 255 bytes to keep the match in (None: the match's own)."""
-        import torch
         if best_engine.n_games != challenger_engine.n_games:
             raise ValueError("the two engines of a match need the same n_games")
         self.best, self.challenger = best_engine, challenger_engine
         self.device, self.n_games = best_engine.device, best_engine.n_games
         self.workspace_bytes = lib.raz_match_workspace_bytes(self.n_games)
-        if workspace is None:
-            workspace = torch.zeros(self.workspace_bytes + 256, dtype=torch.uint8, device=self.device)
-        self._ws = workspace
-        base = self.workspace_base = (workspace.data_ptr() + 255) // 256 * 256
-        if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-                and base + self.workspace_bytes <= workspace.data_ptr() + workspace.numel()):
-            raise ValueError("workspace: a contiguous uint8 device tensor with workspace_bytes behind its first 256-byte boundary")
+        self._ws, self.workspace_base = _workspace(workspace, self.workspace_bytes, self.device)
         self._h = ctypes.c_void_p()
-        check(lib.raz_match_create(best_engine._h, challenger_engine._h, base, self.workspace_bytes, ctypes.byref(self._h)), "raz_match_create")
+        check(lib.raz_match_create(best_engine._h, challenger_engine._h, self.workspace_base, self.workspace_bytes, ctypes.byref(self._h)), "raz_match_create")
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -675,19 +711,13 @@ class DeviceMatch:
         """best_is_black: uint8 / bool device tensor [n_games].  positions: None (the initial position, black to move) or
         (black int64, white int64, player uint8) device tensors [n_games], playable positions.  sims_*: simulations a move."""
         import torch
-        tensors = [best_is_black] + list(positions or ())
-        if positions is not None and len(positions) != 3:
-            raise ValueError("positions is (black, white, player)")
-        for t in tensors:
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == self.n_games):
-                raise ValueError("DeviceMatch.start takes contiguous device tensors of n_games entries (no CPU tensors)")
-        if best_is_black.dtype not in (torch.uint8, torch.bool) or (positions is not None and (
-                positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8)):
-            raise ValueError("best_is_black: uint8 / bool; positions: int64, int64, uint8")
+        dtypes = "best_is_black: uint8 / bool; positions: int64, int64, uint8"
+        b, w, p = _positions("DeviceMatch", positions, self.n_games, leading=[best_is_black], dtypes=dtypes)
+        if best_is_black.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(dtypes)
         if not sims_best:
             raise ValueError("sims_best: simulations a move")
-        self._args = tensors   # (kept alive until the launch has run)
-        b, w, p = (t.data_ptr() for t in positions) if positions is not None else (None, None, None)
+        self._args = [best_is_black] + list(positions or ())   # (kept alive until the launch has run)
         with torch.cuda.device(self.device):
             check(lib.raz_match_start(self._h, best_is_black.data_ptr(), b, w, p, int(sims_best), int(sims_challenger or sims_best),
                                       int(enable_resign), _stream()), "raz_match_start")
@@ -698,26 +728,24 @@ class DeviceMatch:
             check(lib.raz_match_turn(self._h, _stream()), "raz_match_turn")
 
     def stats(self, raise_on_error=True):
-        """{"live", "searching_best", "searching_challenger", "plies", "error"}; raises on the match's error word.  Synchronises."""
+        """{"live", "searching_best", "searching_challenger", "searching": [best, challenger], "plies", "error"}; raises on the match's
+        error word.  Synchronises."""
         import torch
         st = N.RazMatchStats()
         with torch.cuda.device(self.device):
             check(lib.raz_match_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_match_stats_sync")
         if st.error and raise_on_error:
             raise RuntimeError(match_error_text(st.error))
-        return {"live": st.live, "searching_best": st.searching_best, "searching_challenger": st.searching_challenger, "plies": st.plies,
-                "error": st.error}
+        return {"live": st.live, "searching_best": st.searching_best, "searching_challenger": st.searching_challenger,
+                "searching": [st.searching_best, st.searching_challenger], "plies": st.plies, "error": st.error}
 
     def read(self, log=True):
         """(MATCH_GAME [n], MATCH_PLY [n, 64] or None, root visit counts i32 [n, 64, 64] or None) on the host."""
         import torch
-        n = self.n_games
-        games = np.zeros(n, dtype=MATCH_GAME)
-        plies = np.zeros((n, MATCH_MAX_PLIES), dtype=MATCH_PLY) if log else None
-        root_n = np.zeros((n, MATCH_MAX_PLIES, 64), dtype=np.int32) if log else None
+        games = np.zeros(self.n_games, dtype=MATCH_GAME)
+        plies, root_n, plies_ptr, root_n_ptr = _log_arrays(self.n_games, log)
         with torch.cuda.device(self.device):
-            check(lib.raz_match_read(self._h, games.ctypes.data, plies.ctypes.data if log else None, root_n.ctypes.data if log else None,
-                                     _stream()), "raz_match_read")
+            check(lib.raz_match_read(self._h, games.ctypes.data, plies_ptr, root_n_ptr, _stream()), "raz_match_read")
         return games, plies, root_n
 
     def results(self):
@@ -732,7 +760,7 @@ LEAGUE_PAIRING = np.dtype([("black_model", "u1"), ("white_model", "u1"), ("pad0"
 LEAGUE_GAME = np.dtype([("black", "<u8"), ("white", "<u8"), ("player", "u1"), ("black_model", "u1"), ("white_model", "u1"),
                         ("searching", "u1"), ("winner", "u1"), ("blacks", "u1"), ("whites", "u1"), ("n_plies", "u1"), ("flags", "u1"),
                         ("pad8", "u1", (3,)), ("pad", "<u4")])
-LEAGUE_PLY = np.dtype([("who", "u1"), ("action", "i1"), ("turn", "u1"), ("pad", "u1")])
+LEAGUE_PLY = MATCH_PLY   # (`who` is a model index)
 LEAGUE_STATS = np.dtype([("live", "<u4"), ("plies", "<u4"), ("error", "<u4"), ("n_models", "<u4"), ("searching", "<u4", (16,)),
                          ("pad", "<u4", (12,))])
 assert LEAGUE_PAIRING.itemsize == 16 and LEAGUE_GAME.itemsize == 32 and LEAGUE_PLY.itemsize == 4 and LEAGUE_STATS.itemsize == 128
@@ -742,9 +770,8 @@ LEAGUE_ERR_SLOT, LEAGUE_ERR_LOG_FULL, LEAGUE_ERR_PAIRING = 0x100, 0x200, 0x800
 
 
 def league_error_text(error):
-    return (f"league error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
-            f"0x100 a slot left the one-move protocol, 0x200 a game's log is full: the games it hit ended undecided; "
-            f"0x800 a pairing was unsound or lost its slot to a lower game index: the game was not started)")
+    return _error_text("league", error, "0x200 a game's log is full: the games it hit ended undecided; "
+                       "0x800 a pairing was unsound or lost its slot to a lower game index: the game was not started)")
 
 
 def league_pairings(pairings):
@@ -768,11 +795,9 @@ def league_results(games):
 def league_games(games, log, log_n, game_ids=None):
     """The league ply by ply, in the shape of match_games with black_model / white_model and `who` a model index, from
     raz_league_read's host arrays.  game_ids: per game (None: the game's index)."""
-    log, log_n = log.reshape(len(games), LEAGUE_MAX_PLIES), log_n.reshape(len(games), LEAGUE_MAX_PLIES, 64)
+    plies = _ply_lists(games, log, log_n)
     return [{"game_id": g if game_ids is None else game_ids[g], "black_model": int(r["black_model"]), "white_model": int(r["white_model"]),
-             "started": not int(r["flags"]) & LEAGUE_GAME_NOT_STARTED,
-             "plies": [{"who": int(log[g, i]["who"]), "action": int(log[g, i]["action"]), "root_n": log_n[g, i].copy()}
-                       for i in range(int(r["n_plies"]))]} for g, r in enumerate(games)]
+             "started": not int(r["flags"]) & LEAGUE_GAME_NOT_STARTED, "plies": plies[g]} for g, r in enumerate(games)]
 
 
 class DeviceLeague:
@@ -814,13 +839,7 @@ class DeviceLeague:
                 and pairings.numel() and pairings.numel() % LEAGUE_PAIRING.itemsize == 0):
             raise ValueError("DeviceLeague.start takes the pairings as a contiguous uint8 device tensor [n_games, 16] (no CPU tensors)")
         n = pairings.numel() // LEAGUE_PAIRING.itemsize
-        if positions is not None and len(positions) != 3:
-            raise ValueError("positions is (black, white, player)")
-        for t in positions or ():
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
-                raise ValueError("DeviceLeague.start takes contiguous device tensors of n_games entries (no CPU tensors)")
-        if positions is not None and (positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8):
-            raise ValueError("positions: int64, int64, uint8")
+        b, w, p = _positions("DeviceLeague", positions, n)
         if not sims:
             raise ValueError("sims: simulations a move, one number or one per model")
         per_model = [int(sims)] * len(self.engines) if np.isscalar(sims) else [int(s) for s in sims]
@@ -829,15 +848,11 @@ class DeviceLeague:
         if n != self.n_games or not self._h:
             self._destroy()
             need = self.workspace_bytes(n)
-            ws = self._given if self._given is not None else torch.zeros(need + 256, dtype=torch.uint8, device=self.device)
-            base = (ws.data_ptr() + 255) // 256 * 256
-            if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and need and base + need <= ws.data_ptr() + ws.numel()):
-                raise ValueError("workspace: a contiguous uint8 device tensor with workspace_bytes(n_games) behind its first 256-byte boundary")
+            ws, base = _workspace(self._given, need, self.device, what="workspace_bytes(n_games)")
             handles = (ctypes.c_void_p * len(self.engines))(*[e._h.value for e in self.engines])
             check(lib.raz_league_create(handles, len(self.engines), base, need, n, ctypes.byref(self._h)), "raz_league_create")
             self._ws, self.workspace_base, self.n_games = ws, base, n
         self._args = [pairings] + list(positions or ())   # (kept alive until the launches have run)
-        b, w, p = (t.data_ptr() for t in positions) if positions is not None else (None, None, None)
         with torch.cuda.device(self.device):
             check(lib.raz_league_start(self._h, pairings.data_ptr(), b, w, p, (ctypes.c_uint32 * len(per_model))(*per_model),
                                        int(enable_resign), _stream()), "raz_league_start")
@@ -868,13 +883,10 @@ class DeviceLeague:
         """(LEAGUE_GAME [n], LEAGUE_PAIRING [n], LEAGUE_PLY [n, 64] or None, root visit counts i32 [n, 64, 64] or None) on the host."""
         import torch
         self._started("read")
-        n = self.n_games
-        games, pairings = np.zeros(n, dtype=LEAGUE_GAME), np.zeros(n, dtype=LEAGUE_PAIRING)
-        plies = np.zeros((n, LEAGUE_MAX_PLIES), dtype=LEAGUE_PLY) if log else None
-        root_n = np.zeros((n, LEAGUE_MAX_PLIES, 64), dtype=np.int32) if log else None
+        games, pairings = np.zeros(self.n_games, dtype=LEAGUE_GAME), np.zeros(self.n_games, dtype=LEAGUE_PAIRING)
+        plies, root_n, plies_ptr, root_n_ptr = _log_arrays(self.n_games, log)
         with torch.cuda.device(self.device):
-            check(lib.raz_league_read(self._h, games.ctypes.data, pairings.ctypes.data, plies.ctypes.data if log else None,
-                                      root_n.ctypes.data if log else None, _stream()), "raz_league_read")
+            check(lib.raz_league_read(self._h, games.ctypes.data, pairings.ctypes.data, plies_ptr, root_n_ptr, _stream()), "raz_league_read")
         return games, pairings, plies, root_n
 
     def results(self):
@@ -902,8 +914,7 @@ ANALYSIS_ERR_SLOT, ANALYSIS_ERR_BAD_CODE = 0x100, 0x400
 
 
 def analysis_error_text(error):
-    return (f"analysis error word {error:#x} (1 node pool full, 2 table full, 4 records full, 8 path overflow: a slot's engine error; "
-            f"0x100 a slot left the one-move protocol, 0x400 a list entry outside -2..63)")
+    return _error_text("analysis", error, "0x400 a list entry outside -2..63)")
 
 
 class DeviceAnalysis:
@@ -933,14 +944,7 @@ class DeviceAnalysis:
         if not (isinstance(moves, torch.Tensor) and moves.is_cuda and moves.is_contiguous() and moves.dtype == torch.int8 and moves.dim() == 2):
             raise ValueError("DeviceAnalysis.start takes a contiguous int8 device tensor [n_games, max_moves] (no CPU tensors)")
         n, mm = int(moves.shape[0]), int(moves.shape[1])
-        if positions is not None:
-            if len(positions) != 3:
-                raise ValueError("positions is (black, white, player)")
-            for t in positions:
-                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
-                    raise ValueError("DeviceAnalysis.start takes contiguous device tensors of n_games entries (no CPU tensors)")
-            if positions[0].dtype != torch.int64 or positions[1].dtype != torch.int64 or positions[2].dtype != torch.uint8:
-                raise ValueError("positions: int64, int64, uint8")
+        b, w, p = _positions("DeviceAnalysis", positions, n)
         if not sims:
             raise ValueError("sims: simulations a move")
         if (n, mm) != (self.n_games, self.max_moves) or not self._h:
@@ -948,16 +952,12 @@ class DeviceAnalysis:
             need = lib.raz_analysis_workspace_bytes(n, mm)
             if not need:
                 raise ValueError("DeviceAnalysis.start: " + N.last_error())
-            ws = self._given if self._given is not None else (
-                self._ws if self._ws is not None and self._ws.numel() >= need + 256 else torch.zeros(need + 256, dtype=torch.uint8, device=self.device))
-            base = (ws.data_ptr() + 255) // 256 * 256
-            if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and base + need <= ws.data_ptr() + ws.numel()):
-                raise ValueError("workspace: a contiguous uint8 device tensor with workspace_bytes behind its first 256-byte boundary")
+            own = self._ws if self._ws is not None and self._ws.numel() >= need + 256 else None   # (its own, kept while it is large enough)
+            ws, base = _workspace(self._given if self._given is not None else own, need, self.device)
             self._ws, self.workspace_base, self.workspace_bytes = ws, base, need
             check(lib.raz_analysis_create(self.engine._h, self.first_slot, base, need, n, mm, ctypes.byref(self._h)), "raz_analysis_create")
             self.n_games, self.max_moves = n, mm
         self._args = [moves] + list(positions or ())   # (kept alive until the launch has run)
-        b, w, p = (t.data_ptr() for t in positions) if positions is not None else (None, None, None)
         with torch.cuda.device(self.device):
             check(lib.raz_analysis_start(self._h, b, w, p, moves.data_ptr(), int(sims), _stream()), "raz_analysis_start")
 

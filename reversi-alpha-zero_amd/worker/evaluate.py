@@ -101,6 +101,25 @@ class _Side:
         return out
 
 
+def play_on_device(handoff, sides):
+    """Drive a started tournament with the hand-off on the device (engine.DeviceMatch or DeviceLeague: turn, stats, read) to its end and
+    return its read().  sides: the _Side of every entry of stats()["searching"], in that order.  Every engine is stepped while it can have a
+    searching slot; every TURNS_PER_STATS hand-offs the counters are read once per object, which is also when each side's pool is
+    checked and pruned."""
+    st = handoff.stats()   # raises on the error word
+    while st["live"]:
+        for i in range(TURNS_PER_STATS):
+            # (a hand-off may have armed a side that had no searching slot at the last read: only the first iteration knows)
+            for s, searching in zip(sides, st["searching"]):
+                if i or searching:
+                    s.engine.step(STEPS_PER_TURN)
+            handoff.turn()
+        for s in sides:
+            s.busy()
+        st = handoff.stats()
+    return handoff.read()
+
+
 class EvaluateWorker:
     def __init__(self, config, seed=0, device="cuda:0", handoff="host"):
         if handoff not in ("host", "device"):
@@ -180,27 +199,14 @@ class EvaluateWorker:
 
     def _play_on_device(self, sides, best_is_black, first):
         """The match of play_games with the hand-off on the device (engine.DeviceMatch): no ReversiEnv, no raz_engine_set_position call
-        and no record copy per ply.  Both engines are stepped while either can have a searching slot; every TURNS_PER_STATS hand-offs
-        the counters are read once per object, which is also when each side's pool is checked and pruned."""
+        and no record copy per ply."""
         import torch
         from ..engine import DeviceMatch, match_games, match_results
         best, ng = sides[True], sides[False]
         match = DeviceMatch(best.engine, ng.engine)
         match.start(torch.tensor(best_is_black, dtype=torch.uint8, device=self.device), sims_best=best.sims, sims_challenger=ng.sims,
                     enable_resign=True)
-        st = match.stats()   # raises on the match's error word
-        while st["live"]:
-            for i in range(TURNS_PER_STATS):
-                # (a hand-off may have armed a side that had no searching slot at the last read: only the first iteration knows)
-                if i or st["searching_best"]:
-                    best.engine.step(STEPS_PER_TURN)
-                if i or st["searching_challenger"]:
-                    ng.engine.step(STEPS_PER_TURN)
-                match.turn()
-            best.busy()
-            ng.busy()
-            st = match.stats()
-        games, plies, root_n = match.read()
+        games, plies, root_n = play_on_device(match, [best, ng])
         self.last_games = match_games(games, plies, root_n, first_game_id=first)
         return match_results(games)
 

@@ -14,7 +14,7 @@ from logging import getLogger
 import numpy as np
 
 from ..lib.rating import bradley_terry, round_robin, tally
-from .evaluate import STEPS_PER_TURN, TURNS_PER_STATS, _Side
+from .evaluate import _Side, play_on_device
 
 logger = getLogger(__name__)
 
@@ -82,18 +82,7 @@ class LeagueWorker:
         league = DeviceLeague([s.engine for s in sides])
         league.start(torch.from_numpy(pairings.view(np.uint8).reshape(len(games), -1)).to(self.device), sims=[s.sims for s in sides],
                      enable_resign=True)
-        st = league.stats()   # raises on the league's error word
-        while st["live"]:
-            for i in range(TURNS_PER_STATS):
-                # (a hand-off may have armed an engine that had no searching slot at the last read: only the first iteration knows)
-                for m, s in enumerate(sides):
-                    if i or st["searching"][m]:
-                        s.engine.step(STEPS_PER_TURN)
-                league.turn()
-            for s in sides:
-                s.busy()
-            st = league.stats()
-        records, _, plies, root_n = league.read()
+        records, _, plies, root_n = play_on_device(league, sides)
         return records, league_games(records, plies, root_n)
 
     def play(self, out_path=None, keep_games=False):

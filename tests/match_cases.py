@@ -160,14 +160,17 @@ def drive_host(backend, cfg, blobs, n, seed, first, sims, best_is_black, positio
 
 
 def drive_match(backend, cfg, blobs, n, seed, first, sims, best_is_black, positions=None, enable_resign=True, step=4, turn_every=1,
-                max_iterations=100000, guard=None):
-    """The same match through raz_match_*: step both engines `turn_every` times by `step`, hand off, read the counters."""
+                max_iterations=100000, guard=None, after_start=None, error=0):
+    """The same match through raz_match_*: step both engines `turn_every` times by `step`, hand off, read the counters.
+    after_start(sides, match): called once, behind the start; error: the error word the match is to end with."""
     from reversi_alpha_zero_amd.engine import match_games, match_results
     sides = _engines(backend, cfg, blobs, n, seed, first, sims)
     match = backend.match(sides[True], sides[False], **({"guard": guard} if guard is not None else {}))
     match.start(best_is_black, positions, sims, sims, enable_resign)
     st = match.stats()
     assert st["live"] == n and st["searching_best"] + st["searching_challenger"] == n and st["plies"] == 0 and not st["error"]
+    if after_start is not None:
+        after_start(sides, match)
     it = 0
     while st["live"]:
         for _ in range(turn_every):
@@ -177,10 +180,10 @@ def drive_match(backend, cfg, blobs, n, seed, first, sims, best_is_black, positi
         for e in sides.values():
             e.stats()   # raises on engine error flags
         st = match.stats()
-        assert not st["error"], st
+        assert st["error"] in (0, error), st
         it += 1
         assert it < max_iterations, "the match does not end"
-    assert st["searching_best"] == st["searching_challenger"] == 0
+    assert st["error"] == error and st["searching_best"] == st["searching_challenger"] == 0, st
     games, log, root_n = match.read()
     assert st["plies"] == int(games["n_plies"].sum())
     got = match_games(games, log, root_n, first_game_id=first)
@@ -249,3 +252,33 @@ def case_start_positions(backend, blobs, parallel_search_num=1):
     assert_same("resignation", drive_match(backend, rcfg, blobs, 3, 6, 50, 8, [True, False, True], rpos), want)
     off = drive_match(backend, rcfg, blobs, 3, 6, 50, 8, [True, False, True], rpos, enable_resign=False)
     assert all(p[0][1] >= 0 for p in off[0]), "enable_resign = 0 must reach the slots"
+
+
+# ---- case 7: a searching slot that leaves the one-move protocol -------------------------------------------------------------------
+def rearm_outside_one_move(engine, slot, black, white, player, sims):
+    """Arm `slot` again for the side to move of (black, white, player) as a hand-off arms it, but NOT for one move: the slot plays its
+    game on alone and ends in phase done - what csrc/raz_handoff.h's slot_answer calls ERR_SLOT."""
+    own, enemy = (int(black), int(white)) if int(player) == 1 else (int(white), int(black))
+    engine.set_position(slot, own, enemy, 1, sims, enable_resign=True, one_move=False)
+
+
+def case_slot_off_protocol(backend, blobs, parallel_search_num=1):
+    """Game 1's searching slot is re-armed outside one-move mode behind the start: the game ends undecided with error word 0x100 exactly,
+    no engine reports an error flag, the searching counters end at 0, and games 0 and 2 are the games of the undisturbed match."""
+    cfg = engine_cfg(mini_config(parallel_search_num, use_solver_turn=0, use_solver_turn_in_simulation=0))
+    args = (backend, cfg, blobs, 3, 7, 60, 8, [True, False, True], playout_positions(11, 3, 50))
+    clean = drive_match(*args)
+    kept = {}
+
+    def rearm(sides, match):
+        g = match.read()[0][1]
+        assert g["searching"] in (1, 2) and g["n_plies"] == 0
+        rearm_outside_one_move(sides[g["searching"] == 1], 1, g["black"], g["white"], g["player"], 8)
+        kept["match"] = match
+    got = drive_match(*args, after_start=rearm, error=0x100)   # (asserts the final error word, the counters, and e.stats() of both engines every turn)
+    games = kept["match"].read()[0]
+    assert (int(games[1]["searching"]), int(games[1]["winner"]), int(games[1]["n_plies"])) == (0, 0, 0), games[1]
+    assert got[0][1] == [] and got[1][1][0] is None
+    for g in (0, 2):
+        assert len(clean[0][g]) > 0 and games[g]["winner"] != 0
+        assert_same(("beside a slot off the protocol", g), ([got[0][g]], [got[1][g]]), ([clean[0][g]], [clean[1][g]]))

@@ -303,3 +303,9 @@ def test_emulated_analysis_ends_on_an_engine_error(blob):
     with pytest.raises(RuntimeError, match="error flags"):
         e.stats()
     an.check_guard()
+
+
+@pytest.mark.parametrize("psn", [1, 4])
+def test_emulated_collect_fails_a_position_whose_slot_left_the_one_move_protocol(blob, psn):
+    """Case 7: ERR_SLOT, the branch of the shared rule (csrc/raz_handoff.h slot_answer) no engine error reaches."""
+    C.case_slot_off_protocol(Emu, blob, psn)

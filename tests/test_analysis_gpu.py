@@ -277,6 +277,12 @@ def test_game_analyzer_equals_the_host_route_over_two_passes(blob):
     assert d["eval"] == d["top"][0][2] and d["best_move"] == d["top"][0][0] and d["played_diff"] == d["played_eval"] - d["eval"]
 
 
+@pytest.mark.parametrize("psn", [1, 4])
+def test_collect_fails_a_position_whose_slot_left_the_one_move_protocol(blob, psn):
+    """Case 7: ERR_SLOT, the branch of the shared rule (csrc/raz_handoff.h slot_answer) no engine error reaches."""
+    C.case_slot_off_protocol(Gpu, blob, psn)
+
+
 def test_nboard_engine_session_on_the_device(blob):
     """A scripted NBoardEngine session on in-memory streams: go is a fresh ReversiPlayer's move, hint ranks by visits with the best
     last, ping is answered, analyze sends one line per position."""

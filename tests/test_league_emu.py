@@ -1,5 +1,5 @@
-"""CPU: the device league (include/raz.h raz_league_*, csrc/raz_league.h: k_league_claim, k_league_start, k_league_turn) on the WAVE
-EMULATOR - the kernels as they stand, on host memory - against an independent host driver (ReversiEnv objects and one set_position
+"""CPU: the device league (include/raz.h raz_league_*, csrc/raz_league.h: k_league_claim, k_league_start, k_league_turn,
+the bodies of the last two in csrc/raz_handoff.h) on the WAVE EMULATOR - the kernels as they stand, on host memory - against an independent host driver (ReversiEnv objects and one set_position
 call per ply on the mapped slot) and against raz_match_*.  The cases are tests/league_cases.py's; the device runs them in
 tests/test_league_gpu.py."""
 import ctypes
@@ -272,3 +272,9 @@ def test_emulated_league_uploads_a_changed_descriptor_again(blobs3):
     lg.turn()
     assert (lg.workspace() == now).all()   # uploaded once, not on every turn
     lg.check_guard()
+
+
+@pytest.mark.parametrize("psn", [1, 4])
+def test_emulated_league_ends_a_game_whose_slot_left_the_one_move_protocol(blobs3, psn):
+    """Case 5: ERR_SLOT, the branch of the shared rule (csrc/raz_handoff.h slot_answer) no engine error reaches."""
+    L.case_slot_off_protocol(Emu, blobs3, psn)

@@ -215,6 +215,12 @@ def test_league_ends_on_an_engine_error(blobs3):
     lg.check_guard()
 
 
+@pytest.mark.parametrize("psn", [1, 4])
+def test_league_ends_a_game_whose_slot_left_the_one_move_protocol(blobs3, psn):
+    """Case 5: ERR_SLOT, the branch of the shared rule (csrc/raz_handoff.h slot_answer) no engine error reaches."""
+    L.case_slot_off_protocol(Gpu, blobs3, psn)
+
+
 def test_league_survives_set_parts_between_two_turns(blobs3):
     """Case 6: raz_engine_set_parts on one engine, through the engine wrapper, between two turns: the logs equal the run without it.
     (The descriptor does not change with that call; the re-upload itself is asserted on the emulator.)"""

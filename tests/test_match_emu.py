@@ -1,4 +1,5 @@
-"""CPU: the device hand-off between two engines (include/raz.h raz_match_*, csrc/raz_match.h: k_match_start, k_match_turn) on the
+"""CPU: the device hand-off between two engines (include/raz.h raz_match_*, csrc/raz_match.h: k_match_start, k_match_turn, their
+bodies in csrc/raz_handoff.h) on the
 WAVE EMULATOR - the kernels as they stand, on host memory, driven through the library handle of tests/emu_util.py - against an
 independent host driver (ReversiEnv objects and one set_position call per ply) and the golden games of the unmodified reference's
 evaluator.  The cases are tests/match_cases.py's; the device runs them in tests/test_match_gpu.py."""
@@ -234,3 +235,9 @@ def test_emulated_match_ends_on_an_engine_error(blobs):
     with pytest.raises(RuntimeError, match="error flags"):
         a.stats()
     m.check_guard()
+
+
+@pytest.mark.parametrize("psn", [1, 4])
+def test_emulated_match_ends_a_game_whose_slot_left_the_one_move_protocol(blobs, psn):
+    """Case 7: ERR_SLOT, the branch of the shared rule (csrc/raz_handoff.h slot_answer) no engine error reaches."""
+    C.case_slot_off_protocol(Emu, blobs, psn)

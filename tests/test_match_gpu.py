@@ -216,6 +216,12 @@ def test_match_ends_on_an_engine_error(blobs):
     m.check_guard()
 
 
+@pytest.mark.parametrize("psn", [1, 4])
+def test_match_ends_a_game_whose_slot_left_the_one_move_protocol(blobs, psn):
+    """Case 7: ERR_SLOT, the branch of the shared rule (csrc/raz_handoff.h slot_answer) no engine error reaches."""
+    C.case_slot_off_protocol(Gpu, blobs, psn)
+
+
 def test_device_handoff_makes_no_per_game_host_call(nets, monkeypatch):
     """Case 6: during play_games the device route calls neither set_position / set_positions nor pack_records on either engine (the
     host route, counted the same way, calls them once per ply and once per round)."""
