@@ -4,6 +4,7 @@ This is the ONLY bridge between the Python facade and the compute path.  There i
 CPU fallback: if the library is missing this module raises ImportError, and every batched call
 fails with RuntimeError when the HIP runtime reports an error (e.g. no GPU).
 """
+import contextlib
 import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int8, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p, POINTER
@@ -206,17 +207,73 @@ SIGNATURES.update({
     "raz_league_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
-for _name, (_res, _args) in SIGNATURES.items():
-    _fn = getattr(lib, _name)  # AttributeError here == ABI mismatch: fail at import, loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
+
+class Backend:
+    """What a host wrapper (engine.py, agent/trainer.py) needs to reach one build of the C ABI: the library with SIGNATURES applied,
+    its error text, the stream its launches go to, the device guard around them and the allocator of the buffers it is handed.
+    HIP below is the only instance the product makes.  host=True describes a build of the same ABI on host memory (the wave
+    emulator of tests/native/wave_emu, which may lack entries): stream NULL, no guard, CPU tensors."""
+
+    def __init__(self, lib, host=False, empty=None):
+        self.lib, self.host = lib, host
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(lib, name, None) if host else getattr(lib, name)  # AttributeError here == ABI mismatch: fail at import, loudly
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
+        if empty is not None:
+            self.empty = empty
+
+    @staticmethod
+    def empty(*size, **kw):
+        """Allocates what the library is handed as workspace, scratch, weights and cache (torch.empty's signature)."""
+        import torch
+        return torch.empty(*size, **kw)
+
+    def last_error(self) -> str:
+        return (self.lib.raz_last_error() or b"").decode("utf-8", "replace")
+
+    def call(self, name, *args):
+        """lib.<name>(*args); raises RuntimeError on a non-zero status code (SURVEY §8(b) error convention)."""
+        rc = getattr(self.lib, name)(*args)
+        if rc != 0:
+            raise RuntimeError(f"{name} failed (code {rc}): {self.last_error()}")
+
+    def stream(self, device=None):
+        """The stream a launch goes to: torch's current one; NULL for a host library, and for a wrapper whose device is no GPU (it has
+        no stream: the launch fails in the library, with its text)."""
+        return None if self.host or (device is not None and device.type != "cuda") else current_stream_ptr()
+
+    def on(self, device):
+        """The guard a launch runs under: `device` the current one, for the library's own allocations and events."""
+        if device.type != "cuda":
+            return contextlib.nullcontext()
+        import torch
+        return torch.cuda.device(device)
+
+    def synchronize(self, device):
+        if device.type == "cuda":
+            import torch
+            torch.cuda.synchronize(device)
+
+
+class Wrapper:
+    """Base of the host wrappers: `backend` and `device` are set by the subclass.  Every launching entry of include/raz.h ends in the
+    stream and runs with the wrapper's device current - stated here, once."""
+    backend = device = None
+    lib = property(lambda self: self.backend.lib)
+
+    def _launch(self, name, *args):
+        b = self.backend
+        with b.on(self.device):
+            b.call(name, *args, b.stream(self.device))
+
+
+HIP = Backend(lib)
 
 if lib.raz_abi_version() != 3:
     raise ImportError(f"libraz ABI version {lib.raz_abi_version()} != 3 (stale build?)")
 
-
-def last_error() -> str:
-    return (lib.raz_last_error() or b"").decode("utf-8", "replace")
+last_error = HIP.last_error
 
 
 def check(rc: int, what: str = "libraz"):

@@ -191,31 +191,38 @@ class DeviceTrainer:
 
     READ_GRADS, READ_ACT, READ_MEAN, READ_VAR, READ_HIDDEN, READ_POLICY, READ_VALUE = range(7)
 
-    def __init__(self, net, max_batch, device="cuda:0", l2=1e-4, precision="f32"):
+    def __init__(self, net, max_batch, device="cuda:0", l2=1e-4, precision="f32", *, backend=None):
+        """backend: the build of the C ABI to run on (None: _native.HIP, the only one the product makes)."""
         code = precision_code(precision)
-        from .. import _native as N
+        if backend is None:
+            from .. import _native as N   # (here, not at the top: TorchTrainer needs no library)
+            backend = N.HIP
         check_trainable(net)
         self.precision = precision
-        self.N, self.device, self.l2, self.max_batch = N, torch.device(device), float(l2), int(max_batch)
+        self.backend, self.lib, self.device, self.l2, self.max_batch = backend, backend.lib, torch.device(device), float(l2), int(max_batch)
         self.F, self.R, self.V = net.filters, net.res_layers, net.value_fc
         self.handle = ctypes.c_void_p()
-        nbytes = N.lib.raz_trainer_bytes2(self.F, self.R, self.V, self.max_batch, code)   # (precision 0: raz_trainer_bytes / _create to the byte)
+        nbytes = self.lib.raz_trainer_bytes2(self.F, self.R, self.V, self.max_batch, code)   # (precision 0: raz_trainer_bytes / _create to the byte)
         if not nbytes:
             raise ValueError(f"raz_trainer_bytes2 refuses {self.F}x{self.R}x{self.V}, max_batch {self.max_batch}, precision {precision!r}")
-        self.state_floats = N.lib.raz_trainer_state_bytes(self.F, self.R, self.V) // 4
-        with torch.cuda.device(self.device):
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            N.check(N.lib.raz_trainer_create2(self.F, self.R, self.V, self.max_batch, code, self.workspace.data_ptr(), nbytes,
-                                              ctypes.byref(self.handle), N.current_stream_ptr()), "raz_trainer_create2")
+        self.state_floats = self.lib.raz_trainer_state_bytes(self.F, self.R, self.V) // 4
+        self.workspace = self.backend.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._launch("raz_trainer_create2", self.F, self.R, self.V, self.max_batch, code, self.workspace.data_ptr(), nbytes, ctypes.byref(self.handle))
         self.losses = torch.zeros(2, dtype=torch.float32, device=self.device)
         self._shape_net = ReversiNet(self.F, self.R, self.V)
         self.last_batch = 0
         self.from_net(net)
 
+    def _launch(self, name, *args):
+        """lib.<name>(*args, stream) with the trainer's device current (_native.Wrapper's helper; see the import above)."""
+        b = self.backend
+        with b.on(self.device):
+            b.call(name, *args, b.stream(self.device))
+
     def close(self):
         if getattr(self, "handle", None):
-            torch.cuda.synchronize(self.device)
-            self.N.lib.raz_trainer_destroy(self.handle)
+            self.backend.synchronize(self.device)
+            self.lib.raz_trainer_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -227,16 +234,12 @@ class DeviceTrainer:
     # -- state ---------------------------------------------------------------------------------------------------------------
     def set_blob(self, blob):
         t = _tensor(np.ascontiguousarray(blob, dtype=np.float32), self.device)
-        with torch.cuda.device(self.device):
-            self.N.check(self.N.lib.raz_trainer_set_state(self.handle, t.data_ptr(), t.numel() * 4, self.N.current_stream_ptr()),
-                         "raz_trainer_set_state")
-            torch.cuda.current_stream().synchronize()
+        self._launch("raz_trainer_set_state", self.handle, t.data_ptr(), t.numel() * 4)
+        self.backend.synchronize(self.device)
 
     def get_blob(self):
         t = torch.empty(self.state_floats, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self.N.check(self.N.lib.raz_trainer_get_state(self.handle, t.data_ptr(), t.numel() * 4, self.N.current_stream_ptr()),
-                         "raz_trainer_get_state")
+        self._launch("raz_trainer_get_state", self.handle, t.data_ptr(), t.numel() * 4)
         return t.cpu().numpy()
 
     def from_net(self, net, momentum=None):
@@ -266,29 +269,23 @@ class DeviceTrainer:
 
     def backward(self, own, enemy, policy, z, idx):
         own, enemy, policy, z, idx = self._args(own, enemy, policy, z, idx)
-        with torch.cuda.device(self.device):
-            self.N.check(self.N.lib.raz_trainer_backward(self.handle, own.data_ptr(), enemy.data_ptr(), policy.data_ptr(), z.data_ptr(),
-                                                         idx.data_ptr(), idx.numel(), self.l2, self.losses.data_ptr(),
-                                                         self.N.current_stream_ptr()), "raz_trainer_backward")
+        self._launch("raz_trainer_backward", self.handle, own.data_ptr(), enemy.data_ptr(), policy.data_ptr(), z.data_ptr(),
+                     idx.data_ptr(), idx.numel(), self.l2, self.losses.data_ptr())
         self.last_batch = idx.numel()
         return tuple(self.losses.tolist())
 
     def step(self, own, enemy, policy, z, idx, lr, sync=True):
         """sync=False returns the device tensor of the two losses instead of waiting for them."""
         own, enemy, policy, z, idx = self._args(own, enemy, policy, z, idx)
-        with torch.cuda.device(self.device):
-            self.N.check(self.N.lib.raz_trainer_step(self.handle, own.data_ptr(), enemy.data_ptr(), policy.data_ptr(), z.data_ptr(),
-                                                     idx.data_ptr(), idx.numel(), float(lr), self.l2, self.losses.data_ptr(),
-                                                     self.N.current_stream_ptr()), "raz_trainer_step")
+        self._launch("raz_trainer_step", self.handle, own.data_ptr(), enemy.data_ptr(), policy.data_ptr(), z.data_ptr(),
+                     idx.data_ptr(), idx.numel(), float(lr), self.l2, self.losses.data_ptr())
         self.last_batch = idx.numel()
         return tuple(self.losses.tolist()) if sync else self.losses
 
     # -- what the last step left ---------------------------------------------------------------------------------------------
     def read(self, which, layer, shape):
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self.N.check(self.N.lib.raz_trainer_read(self.handle, which, layer, out.data_ptr(), out.numel() * 4,
-                                                     self.N.current_stream_ptr()), "raz_trainer_read")
+        self._launch("raz_trainer_read", self.handle, which, layer, out.data_ptr(), out.numel() * 4)
         return out.cpu()
 
     def _channels(self, layer):

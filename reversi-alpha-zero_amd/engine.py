@@ -1,5 +1,7 @@
-"""Host-side driver objects over the C ABI (include/raz.h): DeviceNet (raz_net_*),
-SelfPlayEngine (raz_engine_*) and DeviceMatch (raz_match_*).  torch is used only to own HBM buffers and the HIP stream.
+"""Host-side driver objects over the C ABI (include/raz.h): DeviceNet (raz_net_*), SelfPlayEngine (raz_engine_*), DeviceMatch
+(raz_match_*), DeviceLeague (raz_league_*) and DeviceAnalysis (raz_analysis_*).  torch is used only to own HBM buffers and the HIP stream.
+How a wrapper reaches its library - the device guard, the call, the stream - is _native.Wrapper._launch over a _native.Backend: HIP for
+the product (there is no CPU fallback: nothing here makes another), the wave emulator's for the CPU tests, which drive these same classes.
 
 SelfPlayEngine replaces, for a batch of concurrent games, the reference's
 SelfPlayWorker.start_game loop (worker/self_play.py:139-175) with two ReversiPlayers per game
@@ -12,7 +14,7 @@ import os
 import numpy as np
 
 from . import _native as N
-from ._native import lib, check
+from ._native import lib, check, current_stream_ptr as _stream  # noqa: F401  (tools and tests take them from here)
 
 NODE_POOL_BYTES_PER_NODE = 232   # csrc/raz_engine.h RAZ_NODE_DEFAULT_BYTES: a game's default pool budget per node of nodes_per_game
 NODE_MAX_BYTES = 704             # RAZ_NODE_MAX_BYTES: 40 B header + 20 B x 33 legal moves
@@ -24,20 +26,15 @@ PLY_HEADER = np.dtype([("own", "<u8"), ("enemy", "<u8"), ("n", "<f8"), ("q", "<f
 assert PLY_HEADER.itemsize == 48
 
 
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 # include/raz.h RAZ_NET_FORM_*
 FORMS = {1: "mfma", 2: "mfma_wave", 3: "wave_lds", 4: "wave_scratch", 5: "wide", 6: "f16x3_repair", 7: "f16x3_no_repair",
          8: "f16_repair", 9: "f16_no_repair"}
 
 
-class DeviceNet:
+class DeviceNet(N.Wrapper):
     """The policy/value net resident in HBM (agent/api.py ReversiModelAPI role, device side)."""
 
-    def __init__(self, blob: bytes, device="cuda:0", force_valu_kernel=False, kernel=None):
+    def __init__(self, blob: bytes, device="cuda:0", force_valu_kernel=False, kernel=None, *, backend=None):
         """kernel: None / "f32" = the exact-f32 kernels chosen by shape (raznet-forward-v1, bit-identical to the CPU oracle);
         "f16x3" = raznet-forward-v2 for filters % 128 == 0: the 3x3 trunk on the f16 matrix cores with split operands, within
         1e-5 of the fp32 graph (include/raz.h raz_net_range_check); "auto" = "f16x3" where supported, else "f32".
@@ -45,16 +42,18 @@ class DeviceNet:
         one matrix instruction per product instead of three.  The trade: a faster trunk for f16's own accuracy - activations and
         weights rounded to 11 bits, outputs NOT within 1e-5 of the graph - which self-play under root noise tolerates and a
         comparison against a reference does not.
-        Test variants: "valu" = k_net_wave; "mfma_wave" = one single-wave workgroup per position."""
+        Test variants: "valu" = k_net_wave; "mfma_wave" = one single-wave workgroup per position.
+        backend: the build of the C ABI to run on (None: _native.HIP, the only one the product makes)."""
         import torch
         import struct
+        self.backend = backend or N.HIP
         magic, ver, F, R, V = struct.unpack_from("<5i", blob, 0)
-        nbytes = lib.raz_net_weight_bytes(F, R, V)
+        nbytes = self.lib.raz_net_weight_bytes(F, R, V)
         if nbytes == 0:
             raise ValueError(f"unsupported net shape F={F} R={R} V={V}")
         self.device = torch.device(device)
         self.filters, self.res_layers, self.value_fc = F, R, V
-        self._weights = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._weights = self.backend.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.c = N.RazNet()
         kernel = "valu" if force_valu_kernel else kernel
         if kernel == "auto":
@@ -62,40 +61,34 @@ class DeviceNet:
         self.kernel_name = {None: "f32", "f32": "f32", "f16x3": "f16x3 split-operand MFMA trunk",
                             "f16": "plain-f16 MFMA trunk (raznet-forward-v3)"}.get(kernel, kernel)
         self.c.reserved = {None: 0, "f32": 0, "valu": 1, "mfma_wave": 2, "f16x3": 4, "f16": 8}[kernel]
-        with torch.cuda.device(self.device):
-            check(lib.raz_net_load(ctypes.byref(self.c), blob, len(blob), self._weights.data_ptr(), nbytes,
-                                   _stream()), "raz_net_load")
+        self._launch("raz_net_load", ctypes.byref(self.c), blob, len(blob), self._weights.data_ptr(), nbytes)
         self._scratch = None
 
     def scratch(self, n):
         import torch
-        need = lib.raz_net_scratch_bytes(self.filters, self.value_fc, n)
+        need = self.lib.raz_net_scratch_bytes(self.filters, self.value_fc, n)
         if need and (self._scratch is None or self._scratch.numel() < need):
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._scratch = self.backend.empty(need, dtype=torch.uint8, device=self.device)
         return (self._scratch.data_ptr(), self._scratch.numel()) if need else (None, 0)
 
     def form(self, n=1):
         """The kernel form a forward of n positions runs on (include/raz.h raz_net_form): one of FORMS' names."""
-        f = lib.raz_net_form(ctypes.byref(self.c), n)
+        f = self.lib.raz_net_form(ctypes.byref(self.c), n)
         if f < 0:
-            check(f, "raz_net_form")
+            raise RuntimeError(f"raz_net_form failed (code {f}): {self.backend.last_error()}")
         return FORMS[f]
 
     def range_ok(self):
         """False when a split-f16 activation left the f16 range since the net was loaded (raz_net_range_check)."""
-        import torch
         v = ctypes.c_int(0)
-        with torch.cuda.device(self.device):
-            check(lib.raz_net_range_check(ctypes.byref(self.c), ctypes.byref(v), _stream()), "raz_net_range_check")
+        self._launch("raz_net_range_check", ctypes.byref(self.c), ctypes.byref(v))
         return v.value == 0
 
     def range_stats(self):
         """(in range, rows repaired): rows of split-f16 forwards since the net was loaded whose activations left the f16 range and
         were evaluated on the exact-f32 chains instead (include/raz.h raz_net_range_stats)."""
-        import torch
         v, r = ctypes.c_int(0), ctypes.c_ulonglong(0)
-        with torch.cuda.device(self.device):
-            check(lib.raz_net_range_stats(ctypes.byref(self.c), ctypes.byref(v), ctypes.byref(r), _stream()), "raz_net_range_stats")
+        self._launch("raz_net_range_stats", ctypes.byref(self.c), ctypes.byref(v), ctypes.byref(r))
         return v.value == 0, int(r.value)
 
     def predict_bitboards(self, own, enemy, active=None):
@@ -107,10 +100,8 @@ class DeviceNet:
         policy = alloc((n, 64), dtype=torch.float32, device=self.device)
         value = alloc((n,), dtype=torch.float32, device=self.device)
         sp, sb = self.scratch(n)
-        with torch.cuda.device(self.device):
-            check(lib.raz_net_forward(ctypes.byref(self.c), own.data_ptr(), enemy.data_ptr(),
-                                      active.data_ptr() if active is not None else None,
-                                      policy.data_ptr(), value.data_ptr(), n, sp, sb, _stream()), "raz_net_forward")
+        self._launch("raz_net_forward", ctypes.byref(self.c), own.data_ptr(), enemy.data_ptr(), active.data_ptr() if active is not None else None,
+                     policy.data_ptr(), value.data_ptr(), n, sp, sb)
         return policy, value
 
 
@@ -169,7 +160,7 @@ def engine_config_from(config, n_games, seed, nodes_per_game, max_plies=72, mirr
     return c
 
 
-class SelfPlayEngine:
+class SelfPlayEngine(N.Wrapper):
     def __init__(self, config, net: DeviceNet, n_games, seed=0, nodes_per_game=None, sims_hint=None,
                  max_plies=72, mirror_updates=None, record_root_w=False, phase_profile=False, single_stream=False, parts=0, inner_max=0,
                  force_slot_kernel=False, leaf_cache_log2=None, leaf_cache_max_discs=0, pool_bytes_per_game=0, fused=False, solver_budget=0,
@@ -184,7 +175,7 @@ class SelfPlayEngine:
         leaf_cache_max_discs: cache only positions with at most that many discs (0 = all)."""
         import torch
         self.net = net
-        self.device = net.device
+        self.backend, self.device = net.backend, net.device
         self.n_games = n_games
         if inner_max == 0 and net.filters >= 128 and int(getattr(config.play, "parallel_search_num", 1) or 1) <= 1:
             # a wide net's forward dwarfs the tree kernel: let a game whose simulations end on finished positions (no net
@@ -223,19 +214,18 @@ class SelfPlayEngine:
         # sleepers (a leaf node each) and finishes <= slots expansions (a mirror node each)
         self.nodes_per_step = 2 * (inner_max or 2) if (self.slots == 1 and not force_slot_kernel) \
             else 3 * self.slots + (inner_max or 2)
-        nbytes = lib.raz_engine_workspace_bytes(ctypes.byref(self.cfg))
+        nbytes = self.lib.raz_engine_workspace_bytes(ctypes.byref(self.cfg))
         if nbytes == 0:
-            raise ValueError("invalid engine config: " + N.last_error())
+            raise ValueError("invalid engine config: " + self.backend.last_error())
         self.workspace_bytes = nbytes
-        self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        self._ws = self.backend.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
         base = (self._ws.data_ptr() + 255) // 256 * 256
         # the engine's own net scratch: DeviceNet.scratch() may re-allocate its buffer for a later, larger predict call
-        need = lib.raz_net_scratch_bytes(net.filters, net.value_fc, n_games * self.slots)
-        self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
+        need = self.lib.raz_net_scratch_bytes(net.filters, net.value_fc, n_games * self.slots)
+        self._scratch = self.backend.empty(need, dtype=torch.uint8, device=self.device) if need else None
         sp, sb = (self._scratch.data_ptr(), need) if need else (None, 0)
         self._h = ctypes.c_void_p()
-        check(lib.raz_engine_create(ctypes.byref(self.cfg), ctypes.byref(net.c), base, nbytes, sp, sb,
-                                    ctypes.byref(self._h)), "raz_engine_create")
+        self.backend.call("raz_engine_create", ctypes.byref(self.cfg), ctypes.byref(net.c), base, nbytes, sp, sb, ctypes.byref(self._h))
         self.record_root_w = record_root_w
         self.max_plies = max_plies
         self._cache = None
@@ -245,27 +235,24 @@ class SelfPlayEngine:
     def attach_leaf_cache(self, log2_entries, max_discs=0):
         """(Re-)attach a cleared evaluation cache; call again after the net's weights changed."""
         import torch
-        need = lib.raz_leaf_cache_bytes(log2_entries, self.n_games * self.slots)
+        need = self.lib.raz_leaf_cache_bytes(log2_entries, self.n_games * self.slots)
         if need == 0:
             raise ValueError("leaf_cache_log2 must be 10..28")
         if self._cache is None or self._cache.numel() < need + 256:
-            self._cache = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            self._cache = self.backend.empty(need + 256, dtype=torch.uint8, device=self.device)
         base = (self._cache.data_ptr() + 255) // 256 * 256
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_set_leaf_cache(self._h, base, need, log2_entries, max_discs, _stream()), "raz_engine_set_leaf_cache")
+        self._launch("raz_engine_set_leaf_cache", self._h, base, need, log2_entries, max_discs)
 
     def leaf_cache_stats(self):
         """{hits, in_batch_duplicates, evaluated, no_room} since the cache was attached (zeros without a cache)."""
-        import torch
         out = (ctypes.c_uint64 * 4)()
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_leaf_cache_stats(self._h, out, _stream()), "raz_engine_leaf_cache_stats")
+        self._launch("raz_engine_leaf_cache_stats", self._h, out)
         return {"hits": out[0], "in_batch_duplicates": out[1], "evaluated": out[2], "no_room": out[3]}
 
     def solver_stats(self):
         """The end-game solver pool's counters since start() (include/raz.h raz_engine_solver_stats)."""
         out = (ctypes.c_uint64 * 15)()
-        check(lib.raz_engine_solver_stats(self._h, out, _stream()), "raz_engine_solver_stats")
+        self._launch("raz_engine_solver_stats", self._h, out)
         tk_slow, tk_pop, tk_all = (int(x) for x in out[:3])
         out = out[3:]
         self._solver_ticks = {"slow_phase_share_of_worker_time": tk_slow / tk_all if tk_all else None, "pops_share": tk_pop / tk_all if tk_all else None,
@@ -280,62 +267,48 @@ class SelfPlayEngine:
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            lib.raz_engine_destroy(h)
+            self.lib.raz_engine_destroy(h)
             self._h = None
 
     def start(self, first_game_id, sims_per_move, n_active=None):
-        import torch
         sims = np.full(self.n_games, sims_per_move, dtype=np.uint32) if np.isscalar(sims_per_move) \
             else np.ascontiguousarray(sims_per_move, dtype=np.uint32)
         assert sims.size == self.n_games
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_start(self._h, first_game_id, sims.ctypes.data,
-                                       self.n_games if n_active is None else n_active, _stream()), "raz_engine_start")
+        self._launch("raz_engine_start", self._h, first_game_id, sims.ctypes.data, self.n_games if n_active is None else n_active)
         self.n_active = self.n_games if n_active is None else n_active
 
     def next_game(self, first_game_id, sims_per_move, n_active=None):
         """The next game of every slot on the slot's tree (reset_mtcs_info_per_game > 1, include/raz.h)."""
-        import torch
         sims = np.full(self.n_games, sims_per_move, dtype=np.uint32) if np.isscalar(sims_per_move) \
             else np.ascontiguousarray(sims_per_move, dtype=np.uint32)
         assert sims.size == self.n_games
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_next_game(self._h, first_game_id, sims.ctypes.data,
-                                           self.n_games if n_active is None else n_active, _stream()), "raz_engine_next_game")
+        self._launch("raz_engine_next_game", self._h, first_game_id, sims.ctypes.data, self.n_games if n_active is None else n_active)
         self.n_active = self.n_games if n_active is None else n_active
 
     def step(self, n=1):
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_step(self._h, n, _stream()), "raz_engine_step")
+        self._launch("raz_engine_step", self._h, n)
 
     def set_parts(self, parts):
-        import torch
-        torch.cuda.synchronize(self.device)
-        check(lib.raz_engine_set_parts(self._h, parts), "raz_engine_set_parts")
+        self.backend.synchronize(self.device)
+        self.backend.call("raz_engine_set_parts", self._h, parts)
 
     def set_solver_pool_every(self, n):
         """Tree launches per round of the end-game solver's pool (include/raz.h raz_engine_set_solver_pool_every): 1 = every step
         waits for the round, n > 1 = the round runs beside the next n - 1 steps, 0 = the library's default.  Between steps only."""
-        import torch
-        torch.cuda.synchronize(self.device)
-        check(lib.raz_engine_set_solver_pool_every(self._h, int(n)), "raz_engine_set_solver_pool_every")
+        self.backend.synchronize(self.device)
+        self.backend.call("raz_engine_set_solver_pool_every", self._h, int(n))
 
     def step_timed(self, n=1):
         """step(n) with HIP events around each kernel; returns (tree_ms, net_ms) summed over n."""
-        import torch
         a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_step_timed(self._h, n, ctypes.byref(a), ctypes.byref(b), _stream()),
-                  "raz_engine_step_timed")
+        self._launch("raz_engine_step_timed", self._h, n, ctypes.byref(a), ctypes.byref(b))
         return a.value, b.value
 
     def phase_profile(self):
         """Per-phase shader-clock ticks summed over games (engine created with phase_profile=True)."""
-        import torch
-        ptr = lib.raz_engine_device_ptr(self._h, 5)
+        ptr = self.lib.raz_engine_device_ptr(self._h, 5)
         off = ptr - self._ws.data_ptr()
-        torch.cuda.synchronize(self.device)
+        self.backend.synchronize(self.device)
         a = self._ws[off:off + self.n_games * 64].cpu().numpy().view(np.uint64).reshape(self.n_games, 8)
         names = ["backup", "controller", "select", "root_noise", "first_arrival_probe", "active_launches",
                  "node_load_wait", "expand_part_of_backup"]
@@ -347,19 +320,17 @@ class SelfPlayEngine:
         i64 [rows] (as shown to the net), "policy" f32 [rows, 64], "value" f32 [rows]}, rows = n_games x parallel_search_num."""
         import torch
         rows = self.n_games * self.slots
-        torch.cuda.synchronize(self.device)
+        self.backend.synchronize(self.device)
 
         def view(which, nbytes, dtype):
-            off = lib.raz_engine_device_ptr(self._h, which) - self._ws.data_ptr()
+            off = self.lib.raz_engine_device_ptr(self._h, which) - self._ws.data_ptr()
             return self._ws[off:off + nbytes].view(dtype)
         return {"active": view(10, rows, torch.uint8), "own": view(11, rows * 8, torch.int64), "enemy": view(12, rows * 8, torch.int64),
                 "policy": view(13, rows * 256, torch.float32).view(rows, 64), "value": view(14, rows * 4, torch.float32)}
 
     def stats(self):
-        import torch
         st = N.RazEngineStats()
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_engine_stats_sync")
+        self._launch("raz_engine_stats_sync", self._h, ctypes.byref(st))
         if st.error_flags:
             raise RuntimeError(f"engine error flags {st.error_flags:#x} (1 node pool full, 2 table full, "
                                f"4 records full, 8 path overflow): enlarge nodes_per_game/max_plies")
@@ -376,47 +347,35 @@ class SelfPlayEngine:
 
     def set_position(self, slot, black, white, player, sims, enable_resign=True, one_move=True):
         """Arm one move for `slot` on an arbitrary position, keeping the slot's tree (include/raz.h)."""
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_set_position(self._h, slot, black, white, player, sims, int(enable_resign),
-                                              int(one_move), _stream()), "raz_engine_set_position")
+        self._launch("raz_engine_set_position", self._h, slot, black, white, player, sims, int(enable_resign), int(one_move))
 
     def set_positions(self, first_slot, black, white, player, sims, enable_resign=True, one_move=True):
         """set_position for len(black) consecutive slots in one launch; black / white: int64 device tensors, player: uint8."""
         import torch
         assert black.is_contiguous() and white.is_contiguous() and player.is_contiguous() and player.dtype == torch.uint8
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_set_positions(self._h, first_slot, black.numel(), black.data_ptr(), white.data_ptr(), player.data_ptr(),
-                                               sims, int(enable_resign), int(one_move), _stream()), "raz_engine_set_positions")
+        self._launch("raz_engine_set_positions", self._h, first_slot, black.numel(), black.data_ptr(), white.data_ptr(), player.data_ptr(), sims,
+                     int(enable_resign), int(one_move))
 
     def stop_thinking(self, slot):
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_stop_thinking(self._h, slot, _stream()), "raz_engine_stop_thinking")
+        self._launch("raz_engine_stop_thinking", self._h, slot)
 
     def adopt_tree(self, slot, player_index):
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_adopt_tree(self._h, slot, player_index, _stream()), "raz_engine_adopt_tree")
+        self._launch("raz_engine_adopt_tree", self._h, slot, player_index)
 
     def read_node(self, slot, black, white, next_player=1, owner=0):
         """(found, W f64[64], N u32[64], P f32[64]) of one key of one slot's tree (include/raz.h)."""
-        import torch
         w = np.zeros(64, dtype=np.float64)
         n = np.zeros(64, dtype=np.uint32)
         p = np.zeros(64, dtype=np.float32)
         found = ctypes.c_int(0)
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_read_node(self._h, slot, black, white, next_player, owner, w.ctypes.data,
-                                           n.ctypes.data, p.ctypes.data, ctypes.byref(found), _stream()),
-                  "raz_engine_read_node")
+        self._launch("raz_engine_read_node", self._h, slot, black, white, next_player, owner, w.ctypes.data, n.ctypes.data, p.ctypes.data,
+                     ctypes.byref(found))
         return bool(found.value), w, n, p
 
     def set_resign_threshold(self, threshold):
         """config.play.resign_threshold changed (worker/self_play.py:250-260); None = no resignation rule."""
-        check(lib.raz_engine_set_resign_threshold(self._h, int(threshold is not None),
-                                                  float(threshold if threshold is not None else 0.0)),
-              "raz_engine_set_resign_threshold")
+        self.backend.call("raz_engine_set_resign_threshold", self._h, int(threshold is not None),
+                          float(threshold if threshold is not None else 0.0))
 
     def pack_records(self, first_slot=0, n_slots=None, plies=None):
         """The records of slots [first_slot, first_slot + n_slots) cut to `plies` plies (None: the largest n_plies
@@ -424,17 +383,14 @@ class SelfPlayEngine:
         raz_engine_pack_records): {"headers": [n, plies, 48] u8, "root_n": [n, plies, 64] i32, "summary": [n, 32] u8}."""
         import torch
         n = self.n_games - first_slot if n_slots is None else n_slots
-        with torch.cuda.device(self.device):
-            if plies is None:
-                mp = ctypes.c_uint32(0)
-                check(lib.raz_engine_records_extent(self._h, first_slot, n, ctypes.byref(mp), _stream()),
-                      "raz_engine_records_extent")
-                plies = max(1, mp.value)
-            hdr = torch.empty((n, plies, 48), dtype=torch.uint8, device=self.device)
-            rn = torch.empty((n, plies, 64), dtype=torch.int32, device=self.device)
-            sm = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
-            check(lib.raz_engine_pack_records(self._h, first_slot, n, plies, hdr.data_ptr(), rn.data_ptr(),
-                                              sm.data_ptr(), _stream()), "raz_engine_pack_records")
+        if plies is None:
+            mp = ctypes.c_uint32(0)
+            self._launch("raz_engine_records_extent", self._h, first_slot, n, ctypes.byref(mp))
+            plies = max(1, mp.value)
+        hdr = torch.empty((n, plies, 48), dtype=torch.uint8, device=self.device)
+        rn = torch.empty((n, plies, 64), dtype=torch.int32, device=self.device)
+        sm = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+        self._launch("raz_engine_pack_records", self._h, first_slot, n, plies, hdr.data_ptr(), rn.data_ptr(), sm.data_ptr())
         return {"headers": hdr, "root_n": rn, "summary": sm}
 
     # ---- continuous batching (include/raz.h raz_engine_harvest) -------------------------------------------------
@@ -452,18 +408,16 @@ class SelfPlayEngine:
         """Move every finished game into `outbox` and restart the freed slots on ids next_game_id, next_game_id + 1, ...
         (len(sims_per_move) of them at most).  resign_threshold: None = the engine's run-time value; else one value per
         new id (None entries / NaN = no resignation rule).  Returns (harvested, restarted, skipped, playing)."""
-        import torch
         sims = np.ascontiguousarray(sims_per_move, dtype=np.uint32)
         thr = None
         if resign_threshold is not None:
             thr = np.array([np.nan if t is None else float(t) for t in resign_threshold], dtype=np.float64)
             assert thr.size == sims.size
         res = N.RazHarvestResult()
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_harvest(self._h, next_game_id, sims.size, sims.ctypes.data if sims.size else None,
-                                         thr.ctypes.data if thr is not None and thr.size else None, outbox["first"], outbox["n"],
-                                         outbox["headers"].data_ptr(), outbox["root_n"].data_ptr(), outbox["summary"].data_ptr(),
-                                         outbox["done"].data_ptr(), ctypes.byref(res), _stream()), "raz_engine_harvest")
+        self._launch("raz_engine_harvest", self._h, next_game_id, sims.size, sims.ctypes.data if sims.size else None,
+                     thr.ctypes.data if thr is not None and thr.size else None, outbox["first"], outbox["n"],
+                     outbox["headers"].data_ptr(), outbox["root_n"].data_ptr(), outbox["summary"].data_ptr(),
+                     outbox["done"].data_ptr(), ctypes.byref(res))
         return res.harvested, res.restarted, res.skipped, res.playing
 
     def play_continuous(self, first_game_id, total_games, sims_of, chunk=64, resign_threshold_of=None, max_steps=100_000_000,
@@ -542,9 +496,7 @@ class SelfPlayEngine:
 
     def gc(self, threshold=0):
         """Prune unreachable nodes in every game whose pool holds >= threshold nodes."""
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_gc(self._h, threshold, _stream()), "raz_engine_gc")
+        self._launch("raz_engine_gc", self._h, threshold)
 
     def run(self, chunk=64, max_steps=10_000_000, allow_gc=True):
         """Step until every active game has finished.  Returns the final stats.  Pools are pruned
@@ -568,7 +520,6 @@ class SelfPlayEngine:
                 raise RuntimeError("engine did not finish within max_steps")
 
     def read_raw(self):
-        import torch
         B, MP = self.n_games, self.max_plies
         hdr = np.zeros((B, MP), dtype=PLY_HEADER)
         root_n = np.zeros((B, MP, 64), dtype=np.uint32)
@@ -580,11 +531,9 @@ class SelfPlayEngine:
         enable_resign = np.zeros(B, dtype=np.uint8)
         fb = np.zeros(B, dtype=np.uint64)
         fw = np.zeros(B, dtype=np.uint64)
-        with torch.cuda.device(self.device):
-            check(lib.raz_engine_read_records(
-                self._h, hdr.ctypes.data, root_n.ctypes.data, root_w.ctypes.data if root_w is not None else None,
-                n_plies.ctypes.data, status.ctypes.data, resigned.ctypes.data, game_id.ctypes.data,
-                enable_resign.ctypes.data, fb.ctypes.data, fw.ctypes.data, _stream()), "raz_engine_read_records")
+        self._launch("raz_engine_read_records", self._h, hdr.ctypes.data, root_n.ctypes.data, root_w.ctypes.data if root_w is not None else None,
+                     n_plies.ctypes.data, status.ctypes.data, resigned.ctypes.data, game_id.ctypes.data,
+                     enable_resign.ctypes.data, fb.ctypes.data, fw.ctypes.data)
         return dict(headers=hdr, root_n=root_n, root_w=root_w, n_plies=n_plies, status=status, resigned=resigned,
                     game_id=game_id, enable_resign=enable_resign, final_black=fb, final_white=fw)
 
@@ -625,23 +574,29 @@ def _error_text(what, error, rest):
             f"0x100 a slot left the one-move protocol, {rest}")
 
 
+def _lies_on(t, device):
+    """t is a tensor in the memory of `device` (an index the device does not name is not compared)."""
+    import torch
+    return isinstance(t, torch.Tensor) and t.device.type == device.type and device.index in (None, t.device.index)
+
+
 def _workspace(given, need, device, what="workspace_bytes"):
     """(tensor, base address): `given`, or the caller's own where it is None, with `need` bytes behind its first 256-byte boundary."""
     import torch
     ws = given if given is not None else torch.zeros(need + 256, dtype=torch.uint8, device=device)
     base = (ws.data_ptr() + 255) // 256 * 256
-    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and need and base + need <= ws.data_ptr() + ws.numel()):
+    if not (_lies_on(ws, device) and ws.dtype == torch.uint8 and ws.is_contiguous() and need and base + need <= ws.data_ptr() + ws.numel()):
         raise ValueError(f"workspace: a contiguous uint8 device tensor with {what} behind its first 256-byte boundary")
     return ws, base
 
 
-def _positions(who, positions, n, leading=(), dtypes="positions: int64, int64, uint8"):
+def _positions(who, positions, n, device, leading=(), dtypes="positions: int64, int64, uint8"):
     """The (black, white, player) pointers raz_*_start takes, three None for positions None; `leading` tensors are held to n entries too."""
     import torch
     if positions is not None and len(positions) != 3:
         raise ValueError("positions is (black, white, player)")
     for t in list(leading) + list(positions or ()):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() == n):
+        if not (_lies_on(t, device) and t.is_contiguous() and t.numel() == n):
             raise ValueError(f"{who}.start takes contiguous device tensors of n_games entries (no CPU tensors)")
     if positions is None:
         return None, None, None
@@ -685,7 +640,7 @@ def match_games(games, log, log_n, first_game_id=0):
     return [{"game_id": first_game_id + g, "best_is_black": bool(r["best_is_black"]), "plies": plies[g]} for g, r in enumerate(games)]
 
 
-class DeviceMatch:
+class DeviceMatch(N.Wrapper):
     """A match of two started engines of the same n_games on the device (include/raz.h raz_match_*): slot g of `best_engine` is the
     best model's player in game g, slot g of `challenger_engine` the challenger's.  The caller steps the engines; turn() hands every
     decided move to the other side's slot where it lies, without a host round trip."""
@@ -695,16 +650,16 @@ class DeviceMatch:
         if best_engine.n_games != challenger_engine.n_games:
             raise ValueError("the two engines of a match need the same n_games")
         self.best, self.challenger = best_engine, challenger_engine
-        self.device, self.n_games = best_engine.device, best_engine.n_games
-        self.workspace_bytes = lib.raz_match_workspace_bytes(self.n_games)
+        self.backend, self.device, self.n_games = best_engine.backend, best_engine.device, best_engine.n_games
+        self.workspace_bytes = self.lib.raz_match_workspace_bytes(self.n_games)
         self._ws, self.workspace_base = _workspace(workspace, self.workspace_bytes, self.device)
         self._h = ctypes.c_void_p()
-        check(lib.raz_match_create(best_engine._h, challenger_engine._h, self.workspace_base, self.workspace_bytes, ctypes.byref(self._h)), "raz_match_create")
+        self.backend.call("raz_match_create", best_engine._h, challenger_engine._h, self.workspace_base, self.workspace_bytes, ctypes.byref(self._h))
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            lib.raz_match_destroy(h)
+            self.lib.raz_match_destroy(h)
             self._h = None
 
     def start(self, best_is_black, positions=None, sims_best=None, sims_challenger=None, enable_resign=True):
@@ -712,28 +667,23 @@ class DeviceMatch:
         (black int64, white int64, player uint8) device tensors [n_games], playable positions.  sims_*: simulations a move."""
         import torch
         dtypes = "best_is_black: uint8 / bool; positions: int64, int64, uint8"
-        b, w, p = _positions("DeviceMatch", positions, self.n_games, leading=[best_is_black], dtypes=dtypes)
+        b, w, p = _positions("DeviceMatch", positions, self.n_games, self.device, leading=[best_is_black], dtypes=dtypes)
         if best_is_black.dtype not in (torch.uint8, torch.bool):
             raise ValueError(dtypes)
         if not sims_best:
             raise ValueError("sims_best: simulations a move")
         self._args = [best_is_black] + list(positions or ())   # (kept alive until the launch has run)
-        with torch.cuda.device(self.device):
-            check(lib.raz_match_start(self._h, best_is_black.data_ptr(), b, w, p, int(sims_best), int(sims_challenger or sims_best),
-                                      int(enable_resign), _stream()), "raz_match_start")
+        self._launch("raz_match_start", self._h, best_is_black.data_ptr(), b, w, p, int(sims_best), int(sims_challenger or sims_best),
+                     int(enable_resign))
 
     def turn(self):
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_match_turn(self._h, _stream()), "raz_match_turn")
+        self._launch("raz_match_turn", self._h)
 
     def stats(self, raise_on_error=True):
         """{"live", "searching_best", "searching_challenger", "searching": [best, challenger], "plies", "error"}; raises on the match's
         error word.  Synchronises."""
-        import torch
         st = N.RazMatchStats()
-        with torch.cuda.device(self.device):
-            check(lib.raz_match_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_match_stats_sync")
+        self._launch("raz_match_stats_sync", self._h, ctypes.byref(st))
         if st.error and raise_on_error:
             raise RuntimeError(match_error_text(st.error))
         return {"live": st.live, "searching_best": st.searching_best, "searching_challenger": st.searching_challenger,
@@ -741,11 +691,9 @@ class DeviceMatch:
 
     def read(self, log=True):
         """(MATCH_GAME [n], MATCH_PLY [n, 64] or None, root visit counts i32 [n, 64, 64] or None) on the host."""
-        import torch
         games = np.zeros(self.n_games, dtype=MATCH_GAME)
         plies, root_n, plies_ptr, root_n_ptr = _log_arrays(self.n_games, log)
-        with torch.cuda.device(self.device):
-            check(lib.raz_match_read(self._h, games.ctypes.data, plies_ptr, root_n_ptr, _stream()), "raz_match_read")
+        self._launch("raz_match_read", self._h, games.ctypes.data, plies_ptr, root_n_ptr)
         return games, plies, root_n
 
     def results(self):
@@ -800,7 +748,7 @@ def league_games(games, log, log_n, game_ids=None):
              "started": not int(r["flags"]) & LEAGUE_GAME_NOT_STARTED, "plies": plies[g]} for g, r in enumerate(games)]
 
 
-class DeviceLeague:
+class DeviceLeague(N.Wrapper):
     """A league of 2..16 started engines, one per model, on the device (include/raz.h raz_league_*): game g names its two models and the
     slot of each model's engine that plays it.  The engines may differ in n_games.  The caller steps the engines; turn() hands every
     decided move to the next mover's slot where it lies, without a host round trip."""
@@ -813,18 +761,18 @@ class DeviceLeague:
             raise ValueError(f"a league has 2..{LEAGUE_MAX_MODELS} engines, one per model")
         if len({id(e) for e in self.engines}) != len(self.engines):
             raise ValueError("every model of a league needs an engine of its own")
-        self.device = self.engines[0].device
+        self.backend, self.device = self.engines[0].backend, self.engines[0].device
         self._given, self._ws, self._h = workspace, None, ctypes.c_void_p()
         self.n_games = 0
 
     def workspace_bytes(self, n_games):
         slots = (ctypes.c_uint32 * len(self.engines))(*[e.n_games for e in self.engines])
-        return int(lib.raz_league_workspace_bytes(len(self.engines), slots, int(n_games)))
+        return int(self.lib.raz_league_workspace_bytes(len(self.engines), slots, int(n_games)))
 
     def _destroy(self):
         h = getattr(self, "_h", None)
         if h:
-            lib.raz_league_destroy(h)
+            self.lib.raz_league_destroy(h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -835,11 +783,11 @@ class DeviceLeague:
         position, black to move) or (black int64, white int64, player uint8) device tensors [n_games], playable positions.
         sims: simulations a move, one number or one per model."""
         import torch
-        if not (isinstance(pairings, torch.Tensor) and pairings.is_cuda and pairings.is_contiguous() and pairings.dtype == torch.uint8
+        if not (_lies_on(pairings, self.device) and pairings.is_contiguous() and pairings.dtype == torch.uint8
                 and pairings.numel() and pairings.numel() % LEAGUE_PAIRING.itemsize == 0):
             raise ValueError("DeviceLeague.start takes the pairings as a contiguous uint8 device tensor [n_games, 16] (no CPU tensors)")
         n = pairings.numel() // LEAGUE_PAIRING.itemsize
-        b, w, p = _positions("DeviceLeague", positions, n)
+        b, w, p = _positions("DeviceLeague", positions, n, self.device)
         if not sims:
             raise ValueError("sims: simulations a move, one number or one per model")
         per_model = [int(sims)] * len(self.engines) if np.isscalar(sims) else [int(s) for s in sims]
@@ -850,30 +798,25 @@ class DeviceLeague:
             need = self.workspace_bytes(n)
             ws, base = _workspace(self._given, need, self.device, what="workspace_bytes(n_games)")
             handles = (ctypes.c_void_p * len(self.engines))(*[e._h.value for e in self.engines])
-            check(lib.raz_league_create(handles, len(self.engines), base, need, n, ctypes.byref(self._h)), "raz_league_create")
+            self.backend.call("raz_league_create", handles, len(self.engines), base, need, n, ctypes.byref(self._h))
             self._ws, self.workspace_base, self.n_games = ws, base, n
         self._args = [pairings] + list(positions or ())   # (kept alive until the launches have run)
-        with torch.cuda.device(self.device):
-            check(lib.raz_league_start(self._h, pairings.data_ptr(), b, w, p, (ctypes.c_uint32 * len(per_model))(*per_model),
-                                       int(enable_resign), _stream()), "raz_league_start")
+        self._launch("raz_league_start", self._h, pairings.data_ptr(), b, w, p, (ctypes.c_uint32 * len(per_model))(*per_model),
+                     int(enable_resign))
 
     def _started(self, what):
         if not self._h:
             raise RuntimeError(f"DeviceLeague.{what}: call start first (raz_league_start)")
 
     def turn(self):
-        import torch
         self._started("turn")
-        with torch.cuda.device(self.device):
-            check(lib.raz_league_turn(self._h, _stream()), "raz_league_turn")
+        self._launch("raz_league_turn", self._h)
 
     def stats(self, raise_on_error=True):
         """{"live", "plies", "error", "n_models", "searching": [per model]}; raises on the league's error word.  Synchronises."""
-        import torch
         self._started("stats")
         st = N.RazLeagueStats()
-        with torch.cuda.device(self.device):
-            check(lib.raz_league_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_league_stats_sync")
+        self._launch("raz_league_stats_sync", self._h, ctypes.byref(st))
         if st.error and raise_on_error:
             raise RuntimeError(league_error_text(st.error))
         return {"live": st.live, "plies": st.plies, "error": st.error, "n_models": st.n_models,
@@ -881,12 +824,10 @@ class DeviceLeague:
 
     def read(self, log=True):
         """(LEAGUE_GAME [n], LEAGUE_PAIRING [n], LEAGUE_PLY [n, 64] or None, root visit counts i32 [n, 64, 64] or None) on the host."""
-        import torch
         self._started("read")
         games, pairings = np.zeros(self.n_games, dtype=LEAGUE_GAME), np.zeros(self.n_games, dtype=LEAGUE_PAIRING)
         plies, root_n, plies_ptr, root_n_ptr = _log_arrays(self.n_games, log)
-        with torch.cuda.device(self.device):
-            check(lib.raz_league_read(self._h, games.ctypes.data, pairings.ctypes.data, plies_ptr, root_n_ptr, _stream()), "raz_league_read")
+        self._launch("raz_league_read", self._h, games.ctypes.data, pairings.ctypes.data, plies_ptr, root_n_ptr)
         return games, pairings, plies, root_n
 
     def results(self):
@@ -917,21 +858,21 @@ def analysis_error_text(error):
     return _error_text("analysis", error, "0x400 a list entry outside -2..63)")
 
 
-class DeviceAnalysis:
+class DeviceAnalysis(N.Wrapper):
     """The retrograde analysis of whole games on one started engine created with record_root_w (include/raz.h raz_analysis_*):
     position j of game g - the position after j list entries - is searched by slot first_slot + g * (max_moves + 1) + j.  The caller
     steps the engine; collect() reduces every decided search where it lies, without a host round trip."""
 
     def __init__(self, engine, first_slot=0, workspace=None):
         """workspace: a uint8 device tensor to keep the analysis in (None: the analysis's own, sized by every start)."""
-        self.engine, self.device, self.first_slot = engine, engine.device, int(first_slot)
+        self.engine, self.backend, self.device, self.first_slot = engine, engine.backend, engine.device, int(first_slot)
         self._given, self._ws, self._h = workspace, None, ctypes.c_void_p()
         self.n_games = self.max_moves = 0
 
     def _destroy(self):
         h = getattr(self, "_h", None)
         if h:
-            lib.raz_analysis_destroy(h)
+            self.lib.raz_analysis_destroy(h)
             self._h = ctypes.c_void_p()
 
     __del__ = _destroy
@@ -941,48 +882,41 @@ class DeviceAnalysis:
         (the initial position, black to move) or (black int64, white int64, player uint8) device tensors [n_games].  sims:
         simulations a move."""
         import torch
-        if not (isinstance(moves, torch.Tensor) and moves.is_cuda and moves.is_contiguous() and moves.dtype == torch.int8 and moves.dim() == 2):
+        if not (_lies_on(moves, self.device) and moves.is_contiguous() and moves.dtype == torch.int8 and moves.dim() == 2):
             raise ValueError("DeviceAnalysis.start takes a contiguous int8 device tensor [n_games, max_moves] (no CPU tensors)")
         n, mm = int(moves.shape[0]), int(moves.shape[1])
-        b, w, p = _positions("DeviceAnalysis", positions, n)
+        b, w, p = _positions("DeviceAnalysis", positions, n, self.device)
         if not sims:
             raise ValueError("sims: simulations a move")
         if (n, mm) != (self.n_games, self.max_moves) or not self._h:
             self._destroy()
-            need = lib.raz_analysis_workspace_bytes(n, mm)
+            need = self.lib.raz_analysis_workspace_bytes(n, mm)
             if not need:
-                raise ValueError("DeviceAnalysis.start: " + N.last_error())
+                raise ValueError("DeviceAnalysis.start: " + self.backend.last_error())
             own = self._ws if self._ws is not None and self._ws.numel() >= need + 256 else None   # (its own, kept while it is large enough)
             ws, base = _workspace(self._given if self._given is not None else own, need, self.device)
             self._ws, self.workspace_base, self.workspace_bytes = ws, base, need
-            check(lib.raz_analysis_create(self.engine._h, self.first_slot, base, need, n, mm, ctypes.byref(self._h)), "raz_analysis_create")
+            self.backend.call("raz_analysis_create", self.engine._h, self.first_slot, base, need, n, mm, ctypes.byref(self._h))
             self.n_games, self.max_moves = n, mm
         self._args = [moves] + list(positions or ())   # (kept alive until the launch has run)
-        with torch.cuda.device(self.device):
-            check(lib.raz_analysis_start(self._h, b, w, p, moves.data_ptr(), int(sims), _stream()), "raz_analysis_start")
+        self._launch("raz_analysis_start", self._h, b, w, p, moves.data_ptr(), int(sims))
 
     def collect(self):
-        import torch
-        with torch.cuda.device(self.device):
-            check(lib.raz_analysis_collect(self._h, _stream()), "raz_analysis_collect")
+        self._launch("raz_analysis_collect", self._h)
 
     def stats(self, raise_on_error=True):
         """{"games", "positions", "armed", "pending", "searched", "solved", "failed", "error"}; raises on the error word.  Synchronises."""
-        import torch
         st = N.RazAnalysisStats()
-        with torch.cuda.device(self.device):
-            check(lib.raz_analysis_stats_sync(self._h, ctypes.byref(st), _stream()), "raz_analysis_stats_sync")
+        self._launch("raz_analysis_stats_sync", self._h, ctypes.byref(st))
         if st.error and raise_on_error:
             raise RuntimeError(analysis_error_text(st.error))
         return {k: getattr(st, k) for k, _ in N.RazAnalysisStats._fields_}
 
     def results(self):
         """(ANALYSIS_GAME [n], ANALYSIS_POS [n, max_moves + 1], ANALYSIS_EVAL [n, max_moves + 1]) on the host.  Synchronises."""
-        import torch
         n, P = self.n_games, self.max_moves + 1
         games, pos, evals = np.zeros(n, dtype=ANALYSIS_GAME), np.zeros((n, P), dtype=ANALYSIS_POS), np.zeros((n, P), dtype=ANALYSIS_EVAL)
-        with torch.cuda.device(self.device):
-            check(lib.raz_analysis_read(self._h, games.ctypes.data, pos.ctypes.data, evals.ctypes.data, _stream()), "raz_analysis_read")
+        self._launch("raz_analysis_read", self._h, games.ctypes.data, pos.ctypes.data, evals.ctypes.data)
         return games, pos, evals
 
 

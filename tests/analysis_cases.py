@@ -1,12 +1,12 @@
 """Shared cases of the retrograde analysis on the device (include/raz.h raz_analysis_*, csrc/raz_analysis.h), run by
 tests/test_analysis_emu.py on the wave emulator and by tests/test_analysis_gpu.py on the device.
 
-A BACKEND gives the cases engines and analyses of one kind:
+Both drive the product's engine.DeviceAnalysis.  A BACKEND (tests/match_cases.py's Adapter) gives the cases
     backend.engine(cfg, blob, n_slots, seed, sims, first_game_id=0, **kw)   a started engine (record_root_w) with every slot idle
     backend.raw(engine)        record 0 of every slot: dict of action, flags, q, n [slots] and root_n, root_w [slots, 64]
     backend.controls(engine)   the slots' control blocks, uint8 [slots, 256] (raz_engine_debug_read, which = 3)
     backend.analysis(engine, n_games, max_moves, first_slot=0, guard=4096)
-                               start(moves int8 [n, max_moves], positions or None, sims), collect(), stats() -> dict,
+                               an AnalysisHarness: start(moves int8 [n, max_moves], positions or None, sims), collect(), stats() -> dict,
                                read() -> (ANALYSIS_GAME [n], ANALYSIS_POS [n, P], ANALYSIS_EVAL [n, P]), workspace(), check_guard()
 
 The EXPECTATION of the replay is py_walk: a pure-Python restatement of ReversiEnv.step (rays walked square by square on integers; none
@@ -24,6 +24,25 @@ INIT = (0x0000000810000000, 0x0000001008000000, 1)
 NONE, SEARCH, PASS_ENTRY, OVER = 0, 1, 2, 3
 END_LIST, END_RULES, END_ILLEGAL = 0, 1, 2
 BAD_CODE = 0x400
+
+
+class AnalysisHarness(M.Guarded):
+    """engine.DeviceAnalysis behind the interface of the cases, in a guarded workspace."""
+
+    def __init__(self, backend, engine, n_games, max_moves, first_slot=0, guard=M.GUARD):
+        from reversi_alpha_zero_amd.engine import DeviceAnalysis
+        super().__init__(backend, engine.lib.raz_analysis_workspace_bytes(n_games, max_moves), guard)
+        self.w, self.n, self.mm = DeviceAnalysis(engine, first_slot=first_slot, workspace=self.given), n_games, max_moves
+
+    def start(self, moves, positions, sims):
+        assert moves.shape == (self.n, self.mm)
+        self.w.start(self.backend.tensor(moves), None if positions is None else tuple(self.backend.tensor(a) for a in positions), sims)
+
+    def collect(self):
+        self.w.collect()
+
+    def read(self):
+        return self.w.results()
 
 
 # ---- the independent walk -----------------------------------------------------------------------------------------------------

@@ -1,10 +1,10 @@
 """Shared cases of the device league (include/raz.h raz_league_*, csrc/raz_league.h), run by tests/test_league_emu.py on the wave
 emulator and by tests/test_league_gpu.py on the device.
 
-A BACKEND gives the cases engines and leagues of one kind - tests/match_cases.py's backend and
-    backend.league(engines, n_games, guard=...)   start(pairings, positions, sims, enable_resign) with pairings a list of
-                                                  (black_model, black_slot, white_model, white_slot), turn(), stats() -> dict,
-                                                  read() -> (games, pairings, plies, root_n), workspace(), check_guard()
+Both drive the product's engine.DeviceLeague.  A BACKEND (tests/match_cases.py's Adapter) gives the cases
+    backend.league(engines, n_games, guard=...)   a LeagueHarness: start(pairings, positions, sims, enable_resign) with pairings a
+                                                  list of (black_model, black_slot, white_model, white_slot), turn(), stats() ->
+                                                  dict, read() -> (games, pairings, plies, root_n), workspace(), check_guard()
     backend.blocks(engine)                        the control blocks of every slot, uint8 [n_games, 256]
 
 The EXPECTATION of every case is drive_host_league: ReversiEnv objects and one set_position call per ply on the mapped slot, which
@@ -12,8 +12,7 @@ looks at no league kernel."""
 import numpy as np
 
 import match_cases as C
-
-GUARD = 4096
+from match_cases import GUARD
 SIZES = (5, 7, 9)          # case 2: the three engines' slots
 SEEDS = (48, 49, 50)
 FIRSTS = (100, 200, 300)
@@ -27,6 +26,29 @@ def mini_blobs3():
     """Three mini nets (16 filters, 1 residual layer, value_fc 16), seeds 1, 2, 3."""
     from reversi_alpha_zero_amd.agent.model import ReversiNet
     return [ReversiNet(16, 1, 16).keras_init_(s).randomize_bn_(s + 1).to_blob() for s in (1, 2, 3)]
+
+
+class LeagueHarness(C.Guarded):
+    """engine.DeviceLeague behind the interface of the cases, in a guarded workspace."""
+
+    def __init__(self, backend, engines, n_games, guard=GUARD):
+        import ctypes
+        from reversi_alpha_zero_amd.engine import DeviceLeague
+        slots = (ctypes.c_uint32 * len(engines))(*[e.n_games for e in engines])
+        super().__init__(backend, engines[0].lib.raz_league_workspace_bytes(len(engines), slots, n_games), guard)
+        self.w, self.n = DeviceLeague(engines, workspace=self.given), n_games
+
+    def start(self, pairings, positions, sims, enable_resign=True):
+        from reversi_alpha_zero_amd.engine import league_pairings
+        assert len(pairings) == self.n
+        pr = self.backend.tensor(league_pairings(pairings).view(np.uint8).reshape(self.n, 16))
+        self.w.start(pr, self.backend.positions(positions), sims, enable_resign)
+
+    def turn(self):
+        self.w.turn()
+
+    def read(self):
+        return self.w.read()
 
 
 def three_engines(backend, cfg, blobs, sims=8, **kw):

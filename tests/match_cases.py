@@ -1,11 +1,13 @@
 """Shared cases of the device hand-off between two engines (include/raz.h raz_match_*, csrc/raz_match.h), run by
 tests/test_match_emu.py on the wave emulator and by tests/test_match_gpu.py on the device.
 
-A BACKEND gives the cases engines and matches of one kind:
+Both drive the PRODUCT's wrappers (engine.SelfPlayEngine, engine.DeviceMatch); a BACKEND - an Adapter below, one instance for the
+emulator's host memory and one for the device - gives the cases engines and matches of its kind:
     backend.engine(cfg, blob, n, seed, sims, **kw)   a started engine with every slot idle (as worker/evaluate.py's _Side makes it)
     backend.answers(engine)                          (actions i8 [n], root visit counts [n, 64]) of every slot's record 0
-    backend.match(best_engine, challenger_engine)    start(best_is_black, positions, sims_best, sims_challenger, enable_resign),
-                                                     turn(), stats() -> dict with "error", read() -> (games, plies, root_n)
+    backend.match(best_engine, challenger_engine)    a MatchHarness: start(best_is_black, positions, sims_best, sims_challenger,
+                                                     enable_resign), turn(), stats() -> dict with "error", read() -> (games, plies,
+                                                     root_n), workspace(), check_guard()
 `cfg` is the namespace an engine is configured from: play = the effective eval play config, play_data.
 
 The EXPECTATION of every case is drive_host: ReversiEnv objects and one set_position call per ply, the loop of
@@ -16,7 +18,117 @@ import os
 import types
 from random import Random
 
+import numpy as np
+
 from conftest import ROOT
+
+GUARD = 4096
+
+
+# ---- the backend of the cases: the product's wrappers on one device ---------------------------------------------------------------
+class Guarded:
+    """The workspace of a product wrapper `w` (set by the subclass) inside a tensor of the backend's device, `guard` bytes of 0x55 on
+    both sides of it."""
+
+    def __init__(self, backend, need, guard):
+        import torch
+        self.backend, self.need = backend, need
+        self.mem = torch.full((guard + need + 256 + guard,), 0x55, dtype=torch.uint8, device=backend.device)
+        self.given = self.mem[guard:guard + need + 256]   # what the wrapper is handed as workspace=
+
+    def _sync(self):
+        self.w.backend.synchronize(self.w.device)
+        return self.w.workspace_base - self.mem.data_ptr()
+
+    def workspace(self):
+        off = self._sync()
+        return self.mem[off:off + self.need].clone().cpu().numpy()
+
+    def check_guard(self):
+        off = self._sync()
+        assert bool((self.mem[off + self.need:] == 0x55).all()) and bool((self.mem[:off] == 0x55).all()), \
+            f"{type(self.w).__name__} wrote outside its workspace"
+
+    def stats(self):
+        return self.w.stats(raise_on_error=False)
+
+
+class MatchHarness(Guarded):
+    """engine.DeviceMatch behind the interface of the cases, in a guarded workspace."""
+
+    def __init__(self, backend, best, challenger, guard=GUARD):
+        from reversi_alpha_zero_amd.engine import DeviceMatch
+        super().__init__(backend, best.lib.raz_match_workspace_bytes(best.n_games), guard)
+        self.w = DeviceMatch(best, challenger, workspace=self.given)
+
+    def start(self, best_is_black, positions, sims_best, sims_challenger, enable_resign=True):
+        bib = self.backend.tensor(np.array([int(b) for b in best_is_black], dtype=np.uint8))
+        self.w.start(bib, self.backend.positions(positions), sims_best, sims_challenger, enable_resign)
+
+    def turn(self):
+        self.w.turn()
+
+    def read(self):
+        return self.w.read()
+
+
+class Adapter:
+    """A backend of the match, league and analysis cases: `device`, and make_engine(cfg, blob, n, **kw) -> a created SelfPlayEngine
+    there (one stream, one part, record_root_w)."""
+
+    def __init__(self, device, make_engine):
+        self.device, self.make_engine = device, make_engine
+
+    def engine(self, cfg, blob, n, seed, sims, first_game_id=0, **kw):
+        e = self.make_engine(cfg, blob, n, seed=seed, sims_hint=sims, max_plies=64, **kw)
+        e.start(first_game_id, sims, n_active=0)
+        return e
+
+    def tensor(self, a):
+        """A host array in the backend's memory (u64 bit patterns travel as int64)."""
+        import torch
+        a = np.ascontiguousarray(a)
+        return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device)
+
+    def positions(self, positions):
+        """[(black, white, player)] or None -> what the wrappers' start takes as positions=."""
+        if positions is None:
+            return None
+        return (self.tensor(np.array([p[0] for p in positions], dtype=np.uint64)), self.tensor(np.array([p[1] for p in positions], dtype=np.uint64)),
+                self.tensor(np.array([p[2] for p in positions], dtype=np.uint8)))
+
+    @staticmethod
+    def answers(e):
+        from reversi_alpha_zero_amd.engine import PLY_HEADER
+        pk = e.pack_records(0, e.n_games, plies=1)
+        return pk["headers"].cpu().numpy().view(PLY_HEADER).reshape(-1)["action"], pk["root_n"].cpu().numpy().reshape(e.n_games, 64)
+
+    @staticmethod
+    def raw(e):
+        """Record 0 of every slot: action, flags, q, n [slots] and root_n, root_w [slots, 64]."""
+        r = e.read_raw()
+        h = r["headers"][:, 0]
+        return dict(action=h["action"], flags=h["flags"], q=h["q"], n=h["n"], root_n=r["root_n"][:, 0], root_w=r["root_w"][:, 0])
+
+    @staticmethod
+    def blocks(e):
+        """The control blocks of every slot, uint8 [n_games, 256] (raz_engine_debug_read, which = 3)."""
+        out = np.zeros((e.n_games, 256), dtype=np.uint8)
+        e.backend.call("raz_engine_debug_read", e._h, 3, 0, out.size, out.ctypes.data)
+        return out
+
+    controls = blocks
+
+    def match(self, best, challenger, guard=GUARD):
+        return MatchHarness(self, best, challenger, guard=guard)
+
+    def league(self, engines, n_games, guard=GUARD):
+        from league_cases import LeagueHarness
+        return LeagueHarness(self, engines, n_games, guard=guard)
+
+    def analysis(self, engine, n_games, max_moves, first_slot=0, guard=GUARD):
+        from analysis_cases import AnalysisHarness
+        return AnalysisHarness(self, engine, n_games, max_moves, first_slot=first_slot, guard=guard)
 
 
 # ---- nets and configurations ------------------------------------------------------------------------------------------------

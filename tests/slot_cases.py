@@ -68,35 +68,23 @@ def phase(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the two engines
-def _gpu(e):
-    return hasattr(e, "device")   # SelfPlayEngine: device memory is torch tensors; EmuEngine: numpy arrays
-
-
 def _lib(e):
-    if _gpu(e):
-        from reversi_alpha_zero_amd import _native
-        return _native.lib
-    return e.lib
+    return e.backend.lib   # (SelfPlayEngine on the device, EmuEngine - the same class - on the emulator's backend)
 
 
 def _stream(e):
-    if _gpu(e):
-        from reversi_alpha_zero_amd.engine import _stream as s
-        return s()
-    return None
+    return e.backend.stream()
 
 
 def dev_from(e, a):
-    """A host array as engine-side memory (u64 bit patterns travel as int64 on the GPU)."""
+    """A host array as engine-side memory (u64 bit patterns travel as int64)."""
+    import torch
     a = np.ascontiguousarray(a)
-    if _gpu(e):
-        import torch
-        return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(e.device)
-    return a
+    return torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(e.device)
 
 
 def host(x):
-    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+    return x.cpu().numpy().copy() if hasattr(x, "cpu") else np.asarray(x)   # (a copy on the emulator too, where .cpu() is the tensor itself)
 
 
 def ptr(x):
@@ -132,13 +120,9 @@ def snapshot(e):
 
 
 def restore(e, snap):
-    if _gpu(e):
-        import torch
-        torch.cuda.synchronize(e.device)
-        e._ws.copy_(snap)
-        torch.cuda.synchronize(e.device)
-    else:
-        np.copyto(e._ws, snap)
+    e.backend.synchronize(e.device)
+    e._ws.copy_(snap)
+    e.backend.synchronize(e.device)
 
 
 def _ok(e, rc, what):

@@ -1,6 +1,6 @@
 """CPU: the retrograde analysis on the device (include/raz.h raz_analysis_*, csrc/raz_analysis.h: k_analysis_start,
-k_analysis_collect) on the WAVE EMULATOR - the kernels as they stand, on host memory, driven through the library handle of
-tests/emu_util.py - against an independent walk of the lists and a second engine armed slot by slot with raz_engine_set_position.
+k_analysis_collect) on the WAVE EMULATOR - the kernels as they stand, on host memory, driven through the product's own wrappers
+(engine.SelfPlayEngine and engine.DeviceAnalysis on tests/emu_util.py's backend) - against an independent walk of the lists and a second engine armed slot by slot with raz_engine_set_position.
 The cases are tests/analysis_cases.py's; the device runs them in tests/test_analysis_gpu.py."""
 import ctypes
 
@@ -9,82 +9,8 @@ import pytest
 
 import analysis_cases as C
 import match_cases as M
-from emu_util import EmuEngine, _check, aligned, load
-
-
-class EmuAnalysis:
-    """engine.DeviceAnalysis on the emulated kernels and numpy arrays.  guard: bytes of 0x55 kept behind the workspace."""
-
-    def __init__(self, engine, n_games, max_moves, first_slot=0, guard=4096, workspace_bytes=None):
-        from reversi_alpha_zero_amd import _native as N
-        self.N, self.lib, self.n, self.mm = N, engine.lib, n_games, max_moves
-        self.bytes = self.lib.raz_analysis_workspace_bytes(n_games, max_moves)
-        give = self.bytes if workspace_bytes is None else workspace_bytes
-        self._mem, self.base = aligned(self.bytes + guard)
-        self.view = np.ctypeslib.as_array((ctypes.c_uint8 * (self.bytes + guard)).from_address(self.base))
-        self.view[:] = 0x55
-        self._h = ctypes.c_void_p()
-        _check(self.lib, self.lib.raz_analysis_create(engine._h, first_slot, self.base, give, n_games, max_moves, ctypes.byref(self._h)), "raz_analysis_create")
-        self._keep = engine
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self.lib.raz_analysis_destroy(self._h)
-            self._h = None
-
-    def start(self, moves, positions, sims):
-        self._moves = np.ascontiguousarray(moves, dtype=np.int8)
-        assert self._moves.shape == (self.n, self.mm)
-        b = w = p = None
-        if positions is not None:
-            self._pos = tuple(np.ascontiguousarray(a) for a in positions)
-            b, w, p = (a.ctypes.data for a in self._pos)
-        _check(self.lib, self.lib.raz_analysis_start(self._h, b, w, p, self._moves.ctypes.data, sims, None), "raz_analysis_start")
-
-    def collect(self):
-        _check(self.lib, self.lib.raz_analysis_collect(self._h, None), "raz_analysis_collect")
-
-    def stats(self):
-        st = self.N.RazAnalysisStats()
-        _check(self.lib, self.lib.raz_analysis_stats_sync(self._h, ctypes.byref(st), None), "raz_analysis_stats_sync")
-        return {k: getattr(st, k) for k, _ in st._fields_}
-
-    def read(self):
-        from reversi_alpha_zero_amd.engine import ANALYSIS_EVAL, ANALYSIS_GAME, ANALYSIS_POS
-        games, pos = np.zeros(self.n, dtype=ANALYSIS_GAME), np.zeros((self.n, self.mm + 1), dtype=ANALYSIS_POS)
-        evals = np.zeros((self.n, self.mm + 1), dtype=ANALYSIS_EVAL)
-        _check(self.lib, self.lib.raz_analysis_read(self._h, games.ctypes.data, pos.ctypes.data, evals.ctypes.data, None), "raz_analysis_read")
-        return games, pos, evals
-
-    def workspace(self):
-        return self.view[:self.bytes].copy()
-
-    def check_guard(self):
-        assert (self.view[self.bytes:] == 0x55).all(), "the analysis wrote past the end of its workspace"
-
-
-class Emu:
-    @staticmethod
-    def engine(cfg, blob, n, seed, sims, first_game_id=0, **kw):
-        e = EmuEngine(cfg, blob, n, seed=seed, sims_hint=sims, max_plies=64, **kw)
-        e.start(first_game_id, sims, n_active=0)
-        return e
-
-    @staticmethod
-    def raw(e):
-        r = e.read_raw()
-        h = r["headers"][:, 0]
-        return dict(action=h["action"], flags=h["flags"], q=h["q"], n=h["n"], root_n=r["root_n"][:, 0], root_w=r["root_w"][:, 0])
-
-    @staticmethod
-    def controls(e):
-        buf = np.zeros((e.n_games, 256), dtype=np.uint8)
-        _check(e.lib, e.lib.raz_engine_debug_read(e._h, 3, 0, buf.size, buf.ctypes.data), "raz_engine_debug_read")
-        return buf
-
-    @staticmethod
-    def analysis(engine, n_games, max_moves, first_slot=0, guard=4096):
-        return EmuAnalysis(engine, n_games, max_moves, first_slot=first_slot, guard=guard)
+from emu_util import EmuEngine, aligned, load
+from test_match_emu import Emu
 
 
 @pytest.fixture(scope="module")
@@ -247,6 +173,8 @@ def test_emulated_analysis_refusals(blob):
     assert lib.raz_analysis_workspace_bytes(2, 128) == 0 and b"max_moves" in lib.raz_last_error()
     assert lib.raz_analysis_workspace_bytes(1, 127) >= 128 * (24 + 128)
     mem, base = aligned(need + 64)
+    view = np.ctypeslib.as_array((ctypes.c_uint8 * (need + 64)).from_address(base))
+    view[:] = 0x55
     h = ctypes.c_void_p()
     controls = Emu.controls(e)
 
@@ -265,21 +193,23 @@ def test_emulated_analysis_refusals(blob):
     create(-1, b"max_moves", mm=0)
     create(-1, b"max_moves", mm=128)
     create(-1, b"n_games", n=0)
-    an = EmuAnalysis(e, 2, 4)
-    st = an.N.RazAnalysisStats()
-    assert lib.raz_analysis_collect(an._h, None) == -4 and b"raz_analysis_start" in lib.raz_last_error()
-    assert lib.raz_analysis_read(an._h, None, None, None, None) == -4 and b"raz_analysis_start" in lib.raz_last_error()
-    assert lib.raz_analysis_stats_sync(an._h, ctypes.byref(st), None) == -4 and b"raz_analysis_start" in lib.raz_last_error()
+    from reversi_alpha_zero_amd import _native as N
+    assert lib.raz_analysis_create(e._h, 0, base, need, 2, 4, ctypes.byref(h)) == 0   # created, not started
+    st = N.RazAnalysisStats()
+    assert lib.raz_analysis_collect(h, None) == -4 and b"raz_analysis_start" in lib.raz_last_error()
+    assert lib.raz_analysis_read(h, None, None, None, None) == -4 and b"raz_analysis_start" in lib.raz_last_error()
+    assert lib.raz_analysis_stats_sync(h, ctypes.byref(st), None) == -4 and b"raz_analysis_start" in lib.raz_last_error()
     assert lib.raz_analysis_collect(None, None) == -1 and b"NULL" in lib.raz_last_error()
     moves = np.full((2, 4), -2, dtype=np.int8)
     one = np.zeros(2, dtype=np.uint64)
-    assert lib.raz_analysis_start(an._h, None, None, None, None, 8, None) == -1 and b"NULL" in lib.raz_last_error()
+    assert lib.raz_analysis_start(h, None, None, None, None, 8, None) == -1 and b"NULL" in lib.raz_last_error()
     assert lib.raz_analysis_start(None, None, None, None, moves.ctypes.data, 8, None) == -1 and b"NULL" in lib.raz_last_error()
-    assert lib.raz_analysis_start(an._h, one.ctypes.data, None, None, moves.ctypes.data, 8, None) == -1 and b"all or none" in lib.raz_last_error()
-    assert lib.raz_analysis_start(an._h, one.ctypes.data, one.ctypes.data, None, moves.ctypes.data, 8, None) == -1 and b"all or none" in lib.raz_last_error()
-    assert lib.raz_analysis_start(an._h, None, None, None, moves.ctypes.data, 0, None) == -1 and b"sims" in lib.raz_last_error()
-    assert (an.view == 0x55).all(), "a refused call wrote into the workspace"
+    assert lib.raz_analysis_start(h, one.ctypes.data, None, None, moves.ctypes.data, 8, None) == -1 and b"all or none" in lib.raz_last_error()
+    assert lib.raz_analysis_start(h, one.ctypes.data, one.ctypes.data, None, moves.ctypes.data, 8, None) == -1 and b"all or none" in lib.raz_last_error()
+    assert lib.raz_analysis_start(h, None, None, None, moves.ctypes.data, 0, None) == -1 and b"sims" in lib.raz_last_error()
+    assert (view == 0x55).all(), "a refused call wrote into the workspace"
     assert (Emu.controls(e) == controls).all(), "a refused call touched the engine"
+    lib.raz_analysis_destroy(h)
 
 
 def test_emulated_analysis_ends_on_an_engine_error(blob):

@@ -1,7 +1,7 @@
 """GPU: the retrograde analysis on the device (include/raz.h raz_analysis_*, engine.DeviceAnalysis) and what is built on it -
 lib/analysis.GameAnalyzer, the NBoard engine's `analyze` - against an independent walk of the lists and a second engine armed slot
-by slot with raz_engine_set_position.  The cases are tests/analysis_cases.py's; the wave emulator runs them in
-tests/test_analysis_emu.py.  Mini net 16x1 at 8 simulations a move unless stated."""
+by slot with raz_engine_set_position.  The cases and the guarded harness around DeviceAnalysis are tests/analysis_cases.py's; the
+wave emulator runs them through the same product wrappers in tests/test_analysis_emu.py.  Mini net 16x1 at 8 simulations a move unless stated."""
 import ctypes
 import io
 
@@ -11,76 +11,9 @@ import torch
 
 import analysis_cases as C
 import match_cases as M
+from test_match_gpu import DEV, Gpu
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GUARD = 4096
-
-
-class GpuAnalysis:
-    """engine.DeviceAnalysis behind the interface of the cases, in a caller's workspace with GUARD bytes of 0x55 around it."""
-
-    def __init__(self, engine, n_games, max_moves, first_slot=0, guard=GUARD):
-        from reversi_alpha_zero_amd._native import lib
-        from reversi_alpha_zero_amd.engine import DeviceAnalysis
-        self.need = lib.raz_analysis_workspace_bytes(n_games, max_moves)
-        self.mem = torch.full((self.need + 256 + guard,), 0x55, dtype=torch.uint8, device=DEV)
-        self.a = DeviceAnalysis(engine, first_slot=first_slot, workspace=self.mem)
-        self.n, self.mm = n_games, max_moves
-
-    def start(self, moves, positions, sims):
-        pos = None
-        if positions is not None:
-            pos = (torch.from_numpy(positions[0].view(np.int64)).to(DEV), torch.from_numpy(positions[1].view(np.int64)).to(DEV),
-                   torch.from_numpy(positions[2]).to(DEV))
-        assert moves.shape == (self.n, self.mm)
-        self.a.start(torch.from_numpy(np.ascontiguousarray(moves)).to(DEV), pos, sims)
-        self.off = self.a.workspace_base - self.mem.data_ptr()
-
-    def collect(self):
-        self.a.collect()
-
-    def stats(self):
-        return self.a.stats(raise_on_error=False)
-
-    def read(self):
-        return self.a.results()
-
-    def workspace(self):
-        torch.cuda.synchronize()
-        return self.mem[self.off:self.off + self.need].cpu().numpy()
-
-    def check_guard(self):
-        torch.cuda.synchronize()
-        assert bool((self.mem[self.off + self.need:] == 0x55).all()) and bool((self.mem[:self.off] == 0x55).all()), \
-            "the analysis wrote outside its workspace"
-
-
-class Gpu:
-    @staticmethod
-    def engine(cfg, blob, n, seed, sims, first_game_id=0, **kw):
-        from reversi_alpha_zero_amd.engine import DeviceNet, SelfPlayEngine
-        e = SelfPlayEngine(cfg, DeviceNet(blob, DEV), n, seed=seed, sims_hint=sims, max_plies=64, parts=1, single_stream=True,
-                           record_root_w=True, **kw)
-        e.start(first_game_id, sims, n_active=0)
-        return e
-
-    @staticmethod
-    def raw(e):
-        r = e.read_raw()
-        h = r["headers"][:, 0]
-        return dict(action=h["action"], flags=h["flags"], q=h["q"], n=h["n"], root_n=r["root_n"][:, 0], root_w=r["root_w"][:, 0])
-
-    @staticmethod
-    def controls(e):
-        from reversi_alpha_zero_amd._native import check, lib
-        buf = np.zeros((e.n_games, 256), dtype=np.uint8)
-        check(lib.raz_engine_debug_read(e._h, 3, 0, buf.size, buf.ctypes.data), "raz_engine_debug_read")
-        return buf
-
-    @staticmethod
-    def analysis(engine, n_games, max_moves, first_slot=0, guard=GUARD):
-        return GpuAnalysis(engine, n_games, max_moves, first_slot=first_slot, guard=guard)
 
 
 @pytest.fixture(scope="module")
@@ -232,7 +165,7 @@ def test_analysis_refusals_and_engine_error(blob):
     assert st["pending"] == 0 and st["failed"] >= 1 and st["failed"] + st["searched"] + st["solved"] == st["armed"] == 5, st
     assert st["error"] & 1 and "node pool full" in analysis_error_text(st["error"])
     with pytest.raises(RuntimeError, match="analysis error word"):
-        an.a.stats()
+        an.w.stats()
     an.check_guard()
 
 

@@ -7,6 +7,7 @@ real libraz.so (tests/test_engine_gpu.py, test_engine_par_gpu.py, test_continuou
 the hardware would not: that every cross-lane operation is reached by all lanes of its wave together."""
 import numpy as np
 import pytest
+import torch
 
 import oracle as O
 from emu_util import EmuEngine
@@ -180,7 +181,8 @@ def test_emulated_series_on_a_carried_tree_and_position_api(golden, blob):
     start = (int(oplies[20]["own"]), int(oplies[20]["enemy"]), 1) if oplies[20]["player"] == 1 else (int(oplies[20]["enemy"]), int(oplies[20]["own"]), 2)
     eng2 = EmuEngine(cfg, blob, n_games=2, seed=3, sims_hint=10)
     eng2.start(200, 10, n_active=0)
-    eng2.set_positions(1, [start[0]], [start[1]], [start[2]], 10, enable_resign=True, one_move=False)   # (the batched form of set_position)
+    b, w = (torch.from_numpy(np.array([x], dtype=np.uint64).view(np.int64)) for x in start[:2])   # (u64 bit patterns travel as int64)
+    eng2.set_positions(1, b, w, torch.tensor([start[2]], dtype=torch.uint8), 10, enable_resign=True, one_move=False)   # (the batched form of set_position)
     for _ in range(6):
         eng2.step(1)
     found, w64, n64, _ = eng2.read_node(1, int(oplies[20]["own"]), int(oplies[20]["enemy"]), 1, 0)
@@ -207,8 +209,8 @@ def test_emulated_byte_limited_pool_and_continuous_batching(golden, blob):
         op, osum = O.selfplay_game(ocfg, blob, 9, 300 + i, 12)
         _same(f"bytes/{i}", plies, summ, op, osum["winner"])
     eng2 = EmuEngine(cfg, blob, n_games=2, seed=9, sims_hint=10, record_root_w=False)
-    outbox = eng2.play_continuous(600, 5, 10)
-    raw = raw_from_packed(outbox["headers"], outbox["root_n"], outbox["summary"])
+    outbox, _ = eng2.play_continuous(600, 5, [10] * 5, chunk=16)
+    raw = raw_from_packed(*(outbox[k].numpy() for k in ("headers", "root_n", "summary")))
     assert list(raw["game_id"]) == [600, 601, 602, 603, 604] and outbox["done"].all()
     for r in range(5):
         op, osum = O.selfplay_game(ocfg, blob, 9, 600 + r, 10)

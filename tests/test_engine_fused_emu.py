@@ -4,6 +4,7 @@ raz_net16_forward_in_wave, `iters` simulations per launch) on the wave emulator 
 unmodified reference's golden games, bit for bit.  The GPU counterparts are in tests/test_engine_gpu.py."""
 import numpy as np
 import pytest
+import torch
 
 import oracle as O
 from emu_util import EmuEngine
@@ -119,7 +120,8 @@ def test_fused_series_position_api_and_continuous_batching(golden, blob):
     start = (int(oplies[20]["own"]), int(oplies[20]["enemy"]), 1) if oplies[20]["player"] == 1 else (int(oplies[20]["enemy"]), int(oplies[20]["own"]), 2)
     eng2 = EmuEngine(cfg, blob, n_games=2, seed=3, sims_hint=10, fused=True)
     eng2.start(200, 10, n_active=0)
-    eng2.set_positions(1, [start[0]], [start[1]], [start[2]], 10, enable_resign=True, one_move=False)
+    b, w = (torch.from_numpy(np.array([x], dtype=np.uint64).view(np.int64)) for x in start[:2])   # (u64 bit patterns travel as int64)
+    eng2.set_positions(1, b, w, torch.tensor([start[2]], dtype=torch.uint8), 10, enable_resign=True, one_move=False)
     for _ in range(6):
         eng2.step(1)
     found, w64, n64, _ = eng2.read_node(1, int(oplies[20]["own"]), int(oplies[20]["enemy"]), 1, 0)
@@ -130,8 +132,8 @@ def test_fused_series_position_api_and_continuous_batching(golden, blob):
     cfg3 = config_of(_variant(golden, "agz"))
     ocfg3 = O.play_cfg_from_config(cfg3)
     eng3 = EmuEngine(cfg3, blob, n_games=2, seed=9, sims_hint=10, record_root_w=False, fused=True)
-    outbox = eng3.play_continuous(600, 5, 10)
-    raw = raw_from_packed(outbox["headers"], outbox["root_n"], outbox["summary"])
+    outbox, _ = eng3.play_continuous(600, 5, [10] * 5, chunk=16)
+    raw = raw_from_packed(*(outbox[k].numpy() for k in ("headers", "root_n", "summary")))
     assert list(raw["game_id"]) == [600, 601, 602, 603, 604] and outbox["done"].all()
     for r in range(5):
         op, osum = O.selfplay_game(ocfg3, blob, 9, 600 + r, 10)

@@ -1,5 +1,6 @@
 """CPU: the device league (include/raz.h raz_league_*, csrc/raz_league.h: k_league_claim, k_league_start, k_league_turn,
-the bodies of the last two in csrc/raz_handoff.h) on the WAVE EMULATOR - the kernels as they stand, on host memory - against an independent host driver (ReversiEnv objects and one set_position
+the bodies of the last two in csrc/raz_handoff.h) on the WAVE EMULATOR - the kernels as they stand, on host memory, driven through the
+product's own wrappers (engine.SelfPlayEngine and engine.DeviceLeague on tests/emu_util.py's backend) - against an independent host driver (ReversiEnv objects and one set_position
 call per ply on the mapped slot) and against raz_match_*.  The cases are tests/league_cases.py's; the device runs them in
 tests/test_league_gpu.py."""
 import ctypes
@@ -9,81 +10,8 @@ import pytest
 
 import league_cases as L
 import match_cases as C
-from emu_util import EmuEngine, _check, aligned, load
-from test_match_emu import Emu as EmuOfMatch, match_of_65
-
-
-class EmuLeague:
-    """engine.DeviceLeague on the emulated kernels and numpy arrays, the workspace between `guard` bytes of 0x55 on both sides."""
-
-    def __init__(self, engines, n_games, guard=L.GUARD, workspace_bytes=None):
-        from reversi_alpha_zero_amd import _native as N
-        assert guard % 256 == 0
-        self.N, self.lib, self.n, self.engines = N, engines[0].lib, n_games, list(engines)
-        slots = (ctypes.c_uint32 * len(engines))(*[e.n_games for e in engines])
-        self.bytes = self.lib.raz_league_workspace_bytes(len(engines), slots, n_games)
-        give = self.bytes if workspace_bytes is None else workspace_bytes
-        self._mem, start = aligned(self.bytes + 2 * guard)
-        self.guard, self.base = guard, start + guard
-        self.view = np.ctypeslib.as_array((ctypes.c_uint8 * (self.bytes + 2 * guard)).from_address(start))
-        self.view[:] = 0x55
-        self._h = ctypes.c_void_p()
-        handles = (ctypes.c_void_p * len(engines))(*[e._h.value for e in engines])
-        _check(self.lib, self.lib.raz_league_create(handles, len(engines), self.base, give, n_games, ctypes.byref(self._h)), "raz_league_create")
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self.lib.raz_league_destroy(self._h)
-            self._h = None
-
-    def start(self, pairings, positions, sims, enable_resign=True):
-        from reversi_alpha_zero_amd.engine import league_pairings
-        self._pairings = league_pairings(pairings)
-        b = w = p = None
-        if positions is not None:
-            self._pos = (np.array([x[0] for x in positions], dtype=np.uint64), np.array([x[1] for x in positions], dtype=np.uint64),
-                         np.array([x[2] for x in positions], dtype=np.uint8))
-            b, w, p = (a.ctypes.data for a in self._pos)
-        per = [sims] * len(self.engines) if np.isscalar(sims) else list(sims)
-        _check(self.lib, self.lib.raz_league_start(self._h, self._pairings.ctypes.data, b, w, p, (ctypes.c_uint32 * len(per))(*per),
-                                                   int(enable_resign), None), "raz_league_start")
-
-    def turn(self):
-        _check(self.lib, self.lib.raz_league_turn(self._h, None), "raz_league_turn")
-
-    def stats(self):
-        st = self.N.RazLeagueStats()
-        _check(self.lib, self.lib.raz_league_stats_sync(self._h, ctypes.byref(st), None), "raz_league_stats_sync")
-        return {"live": st.live, "plies": st.plies, "error": st.error, "n_models": st.n_models,
-                "searching": [int(x) for x in st.searching[:len(self.engines)]]}
-
-    def read(self):
-        from reversi_alpha_zero_amd.engine import LEAGUE_GAME, LEAGUE_MAX_PLIES, LEAGUE_PAIRING, LEAGUE_PLY
-        games, pairings = np.zeros(self.n, dtype=LEAGUE_GAME), np.zeros(self.n, dtype=LEAGUE_PAIRING)
-        plies = np.zeros((self.n, LEAGUE_MAX_PLIES), dtype=LEAGUE_PLY)
-        root_n = np.zeros((self.n, LEAGUE_MAX_PLIES, 64), dtype=np.int32)
-        _check(self.lib, self.lib.raz_league_read(self._h, games.ctypes.data, pairings.ctypes.data, plies.ctypes.data, root_n.ctypes.data, None),
-               "raz_league_read")
-        return games, pairings, plies, root_n
-
-    def workspace(self):
-        return self.view[self.guard:self.guard + self.bytes].copy()
-
-    def check_guard(self):
-        assert (self.view[:self.guard] == 0x55).all() and (self.view[self.guard + self.bytes:] == 0x55).all(), \
-            "the league wrote outside its workspace"
-
-
-class Emu(EmuOfMatch):
-    @staticmethod
-    def league(engines, n_games, guard=L.GUARD):
-        return EmuLeague(engines, n_games, guard=guard)
-
-    @staticmethod
-    def blocks(e):
-        out = np.zeros((e.n_games, 256), dtype=np.uint8)
-        _check(e.lib, e.lib.raz_engine_debug_read(e._h, 3, 0, out.size, out.ctypes.data), "raz_engine_debug_read")
-        return out
+from emu_util import EmuEngine, aligned, load
+from test_match_emu import Emu, match_of_65
 
 
 @pytest.fixture(scope="module")
@@ -248,7 +176,7 @@ def test_emulated_league_uploads_a_changed_descriptor_again(blobs3):
     positions = L.case2_positions()
 
     def set_parts(engines, league):
-        _check(engines[1].lib, engines[1].lib.raz_engine_set_parts(engines[1]._h, 4), "raz_engine_set_parts")
+        engines[1].backend.call("raz_engine_set_parts", engines[1]._h, 4)
     L.assert_same("set_parts between two turns", L.drive_league(Emu, make, L.PAIRINGS, positions, between=set_parts),
                   L.drive_league(Emu, make, L.PAIRINGS, positions))
     engines = make()

@@ -1,6 +1,7 @@
 """GPU: the device league (include/raz.h raz_league_*, engine.DeviceLeague) and what is built on it - worker/league.py's LeagueWorker,
-self_opt.start(archive_generations=True) - against an independent host driver and raz_match_*.  The cases are
-tests/league_cases.py's; the wave emulator runs them in tests/test_league_emu.py."""
+self_opt.start(archive_generations=True) - against an independent host driver and raz_match_*.  The cases and the guarded harness
+around DeviceLeague are tests/league_cases.py's; the wave emulator runs them through the same product wrappers in
+tests/test_league_emu.py."""
 import ctypes
 import os
 
@@ -10,63 +11,9 @@ import torch
 
 import league_cases as L
 import match_cases as C
-from test_match_gpu import DEV, Gpu as GpuOfMatch, _self_opt_config
+from test_match_gpu import DEV, Gpu, _self_opt_config
 
 pytestmark = pytest.mark.gpu
-
-
-class GpuLeague:
-    """engine.DeviceLeague behind the interface of the cases, in a caller's workspace with `guard` bytes of 0x55 on both sides."""
-
-    def __init__(self, engines, n_games, guard=L.GUARD):
-        from reversi_alpha_zero_amd.engine import DeviceLeague
-        self.m = DeviceLeague(engines, workspace=None)
-        self.need = self.m.workspace_bytes(n_games)
-        self.mem = torch.full((guard + self.need + 256 + guard,), 0x55, dtype=torch.uint8, device=DEV)
-        self.m._given = self.mem[guard:guard + self.need + 256]
-        self.n = n_games
-
-    def start(self, pairings, positions, sims, enable_resign=True):
-        from reversi_alpha_zero_amd.engine import league_pairings
-        assert len(pairings) == self.n
-        pos = None
-        if positions is not None:
-            u = lambda xs: torch.from_numpy(np.array(xs, dtype=np.uint64).view(np.int64)).to(DEV)
-            pos = (u([p[0] for p in positions]), u([p[1] for p in positions]), torch.tensor([p[2] for p in positions], dtype=torch.uint8, device=DEV))
-        pr = torch.from_numpy(league_pairings(pairings).view(np.uint8).reshape(self.n, 16)).to(DEV)
-        self.m.start(pr, pos, sims, enable_resign)
-        self.off = self.m.workspace_base - self.mem.data_ptr()
-
-    def turn(self):
-        self.m.turn()
-
-    def stats(self):
-        return self.m.stats(raise_on_error=False)
-
-    def read(self):
-        return self.m.read()
-
-    def workspace(self):
-        torch.cuda.synchronize()
-        return self.mem[self.off:self.off + self.need].cpu().numpy()
-
-    def check_guard(self):
-        torch.cuda.synchronize()
-        assert bool((self.mem[self.off + self.need:] == 0x55).all()) and bool((self.mem[:self.off] == 0x55).all()), \
-            "the league wrote outside its workspace"
-
-
-class Gpu(GpuOfMatch):
-    @staticmethod
-    def league(engines, n_games, guard=L.GUARD):
-        return GpuLeague(engines, n_games, guard=guard)
-
-    @staticmethod
-    def blocks(e):
-        from reversi_alpha_zero_amd._native import check, lib
-        out = np.zeros((e.n_games, 256), dtype=np.uint8)
-        check(lib.raz_engine_debug_read(e._h, 3, 0, out.size, out.ctypes.data), "raz_engine_debug_read")
-        return out
 
 
 @pytest.fixture(scope="module")
@@ -165,13 +112,13 @@ def test_league_refusals_and_edges(blobs3):
         DeviceLeague([a, b, a])
     with pytest.raises(ValueError, match="2..16"):
         DeviceLeague([a])
-    lg = GpuLeague(engines, n)
+    lg = Gpu.league(engines, n)
     with pytest.raises(RuntimeError, match="raz_league_start"):
-        lg.m.turn()
+        lg.w.turn()
     with pytest.raises(ValueError, match="CPU"):
-        lg.m.start(pr.cpu(), sims=8)
+        lg.w.start(pr.cpu(), sims=8)
     with pytest.raises(ValueError, match="CPU"):
-        lg.m.start(pr, positions=(torch.zeros(n, dtype=torch.int64),) * 2 + (torch.ones(n, dtype=torch.uint8),), sims=8)
+        lg.w.start(pr, positions=(torch.zeros(n, dtype=torch.int64),) * 2 + (torch.ones(n, dtype=torch.uint8),), sims=8)
     with pytest.raises(ValueError, match="workspace"):
         DeviceLeague(engines, workspace=torch.zeros(need - 1, dtype=torch.uint8, device=DEV)).start(pr, sims=8)
     with pytest.raises(RuntimeError, match="raz_engine_start"):
@@ -197,7 +144,7 @@ def test_league_ends_on_an_engine_error(blobs3):
     from reversi_alpha_zero_amd.engine import league_error_text
     cfg = C.engine_cfg(C.mini_config(1))
     engines = [Gpu.engine(cfg, blobs3[0], 3, 0, 8, nodes_per_game=40), Gpu.engine(cfg, blobs3[1], 2, 1, 8), Gpu.engine(cfg, blobs3[2], 2, 2, 8)]
-    lg = GpuLeague(engines, 3)
+    lg = Gpu.league(engines, 3)
     lg.start([(0, 2, 1, 0), (2, 1, 0, 0), (0, 1, 2, 0)], C.playout_positions(5, 3, 24), 8)
     for it in range(400):
         for e in engines:
@@ -208,7 +155,7 @@ def test_league_ends_on_an_engine_error(blobs3):
             break
     assert st["live"] == 0 and sum(st["searching"]) == 0 and st["error"] & 1, st
     with pytest.raises(RuntimeError, match="node pool full") as err:
-        lg.m.stats()
+        lg.w.stats()
     assert str(err.value) == league_error_text(st["error"])
     games = lg.read()[0]
     assert (games["searching"] == 0).all() and (games["winner"] == 0).any()

@@ -1,7 +1,7 @@
 """CPU: the device hand-off between two engines (include/raz.h raz_match_*, csrc/raz_match.h: k_match_start, k_match_turn, their
 bodies in csrc/raz_handoff.h) on the
-WAVE EMULATOR - the kernels as they stand, on host memory, driven through the library handle of tests/emu_util.py - against an
-independent host driver (ReversiEnv objects and one set_position call per ply) and the golden games of the unmodified reference's
+WAVE EMULATOR - the kernels as they stand, on host memory, driven through the product's own wrappers (engine.SelfPlayEngine and
+engine.DeviceMatch on tests/emu_util.py's backend) - against an independent host driver (ReversiEnv objects and one set_position call per ply) and the golden games of the unmodified reference's
 evaluator.  The cases are tests/match_cases.py's; the device runs them in tests/test_match_gpu.py."""
 import ctypes
 
@@ -9,78 +9,10 @@ import numpy as np
 import pytest
 
 import match_cases as C
-from emu_util import EmuEngine, _check, aligned, load
+from emu_util import EmuEngine, aligned, load
 
 
-class EmuMatch:
-    """engine.DeviceMatch on the emulated kernels and numpy arrays.  guard: bytes of 0x55 kept behind the workspace."""
-
-    def __init__(self, best, challenger, guard=4096, workspace_bytes=None):
-        from reversi_alpha_zero_amd import _native as N
-        self.N, self.lib, self.n = N, best.lib, best.n_games
-        self.bytes = self.lib.raz_match_workspace_bytes(self.n)
-        give = self.bytes if workspace_bytes is None else workspace_bytes
-        self._mem, self.base = aligned(self.bytes + guard)
-        self.guard = guard
-        self.view = np.ctypeslib.as_array((ctypes.c_uint8 * (self.bytes + guard)).from_address(self.base))
-        self.view[self.bytes:] = 0x55
-        self._h = ctypes.c_void_p()
-        _check(self.lib, self.lib.raz_match_create(best._h, challenger._h, self.base, give, ctypes.byref(self._h)), "raz_match_create")
-        self._keep = (best, challenger)
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            self.lib.raz_match_destroy(self._h)
-            self._h = None
-
-    def start(self, best_is_black, positions, sims_best, sims_challenger, enable_resign=True):
-        bib = np.ascontiguousarray(best_is_black, dtype=np.uint8)
-        b = w = p = None
-        if positions is not None:
-            self._pos = (np.array([x[0] for x in positions], dtype=np.uint64), np.array([x[1] for x in positions], dtype=np.uint64),
-                         np.array([x[2] for x in positions], dtype=np.uint8))
-            b, w, p = (a.ctypes.data for a in self._pos)
-        _check(self.lib, self.lib.raz_match_start(self._h, bib.ctypes.data, b, w, p, sims_best, sims_challenger, int(enable_resign), None), "raz_match_start")
-
-    def turn(self):
-        _check(self.lib, self.lib.raz_match_turn(self._h, None), "raz_match_turn")
-
-    def stats(self):
-        st = self.N.RazMatchStats()
-        _check(self.lib, self.lib.raz_match_stats_sync(self._h, ctypes.byref(st), None), "raz_match_stats_sync")
-        return {"live": st.live, "searching_best": st.searching_best, "searching_challenger": st.searching_challenger, "plies": st.plies,
-                "error": st.error}
-
-    def read(self):
-        from reversi_alpha_zero_amd.engine import MATCH_GAME, MATCH_MAX_PLIES, MATCH_PLY
-        games = np.zeros(self.n, dtype=MATCH_GAME)
-        plies = np.zeros((self.n, MATCH_MAX_PLIES), dtype=MATCH_PLY)
-        root_n = np.zeros((self.n, MATCH_MAX_PLIES, 64), dtype=np.int32)
-        _check(self.lib, self.lib.raz_match_read(self._h, games.ctypes.data, plies.ctypes.data, root_n.ctypes.data, None), "raz_match_read")
-        return games, plies, root_n
-
-    def workspace(self):
-        return self.view[:self.bytes].copy()
-
-    def check_guard(self):
-        assert (self.view[self.bytes:] == 0x55).all(), "the match wrote past the end of its workspace"
-
-
-class Emu:
-    @staticmethod
-    def engine(cfg, blob, n, seed, sims, first_game_id=0, **kw):
-        e = EmuEngine(cfg, blob, n, seed=seed, sims_hint=sims, max_plies=64, **kw)
-        e.start(first_game_id, sims, n_active=0)
-        return e
-
-    @staticmethod
-    def answers(e):
-        raw = e.read_raw()
-        return raw["headers"][:, 0]["action"], raw["root_n"][:, 0]
-
-    @staticmethod
-    def match(best, challenger, guard=4096):
-        return EmuMatch(best, challenger, guard=guard)
+Emu = C.Adapter("cpu", EmuEngine)   # the emulator's instance of the cases' backend: the product's wrappers on host memory
 
 
 @pytest.fixture(scope="module")
@@ -160,25 +92,24 @@ def test_emulated_match_refusals_and_edges(blobs):
     a, b, c = Emu.engine(cfg, blobs[0], 2, 0, 8), Emu.engine(cfg, blobs[1], 2, 1, 8), Emu.engine(cfg, blobs[1], 3, 1, 8)
     idle = EmuEngine(cfg, blobs[1], 2, seed=1, sims_hint=8, max_plies=64)   # created, not started
 
-    def refused(code, text, *args, **kw):
-        with pytest.raises(RuntimeError, match=text) as e:
-            EmuMatch(*args, **kw)
-        assert f"code {code}" in str(e.value)
-    refused(-1, "differ in n_games", a, c)
-    refused(-4, "raz_engine_start", a, idle)
-    refused(-1, "smaller than raz_match_workspace_bytes", a, b, workspace_bytes=lib.raz_match_workspace_bytes(2) - 1)
     h = ctypes.c_void_p()
     mem, base = aligned(lib.raz_match_workspace_bytes(2) + 64)
+
+    def refused(code, text, x, y, workspace_bytes=lib.raz_match_workspace_bytes(2)):
+        assert lib.raz_match_create(x._h, y._h, base, workspace_bytes, ctypes.byref(h)) == code and text in lib.raz_last_error(), lib.raz_last_error()
+    refused(-1, b"differ in n_games", a, c)
+    refused(-4, b"raz_engine_start", a, idle)
+    refused(-1, b"smaller than raz_match_workspace_bytes", a, b, workspace_bytes=lib.raz_match_workspace_bytes(2) - 1)
     assert lib.raz_match_create(a._h, b._h, base + 64, lib.raz_match_workspace_bytes(2), ctypes.byref(h)) == -1 and b"aligned" in lib.raz_last_error()
     assert lib.raz_match_create(a._h, None, base, lib.raz_match_workspace_bytes(2), ctypes.byref(h)) == -1 and b"NULL" in lib.raz_last_error()
     assert lib.raz_match_workspace_bytes(0) == 0
     assert lib.raz_match_workspace_bytes(65) - lib.raz_match_workspace_bytes(1) >= 64 * (32 + 64 * 4 + 64 * 256)
-    m = EmuMatch(a, b)
-    assert lib.raz_match_turn(m._h, None) == -4 and b"raz_match_start" in lib.raz_last_error()
+    m = Emu.match(a, b)
+    assert lib.raz_match_turn(m.w._h, None) == -4 and b"raz_match_start" in lib.raz_last_error()
     bib = np.array([1, 0], dtype=np.uint8)
     one = np.zeros(2, dtype=np.uint64)
-    assert lib.raz_match_start(m._h, bib.ctypes.data, one.ctypes.data, None, None, 8, 8, 1, None) == -1 and b"all or none" in lib.raz_last_error()
-    assert lib.raz_match_start(m._h, bib.ctypes.data, None, None, None, 0, 8, 1, None) == -1 and b"sims" in lib.raz_last_error()
+    assert lib.raz_match_start(m.w._h, bib.ctypes.data, one.ctypes.data, None, None, 8, 8, 1, None) == -1 and b"all or none" in lib.raz_last_error()
+    assert lib.raz_match_start(m.w._h, bib.ctypes.data, None, None, None, 0, 8, 1, None) == -1 and b"sims" in lib.raz_last_error()
     # no decided slot: a hand-off changes no byte of the workspace (nor of the engines' control blocks)
     m.start([1, 0], None, 8, 8)
     before = m.workspace()
@@ -194,7 +125,7 @@ def test_emulated_match_turn_without_a_decided_slot_changes_nothing(blobs):
     byte for byte, and writes nothing behind it."""
     cfg = C.engine_cfg(C.mini_config(4))
     a, b = Emu.engine(cfg, blobs[0], 65, 0, 8), Emu.engine(cfg, blobs[1], 65, 1, 8)
-    m = EmuMatch(a, b)
+    m = Emu.match(a, b)
     m.start([g % 2 for g in range(65)], C.playout_positions(2, 65, 20), 8, 8)
     before = m.workspace()
     games = m.read()[0]
@@ -219,7 +150,7 @@ def test_emulated_match_ends_on_an_engine_error(blobs):
         EmuEngine(cfg, blobs[0], 2, seed=0, sims_hint=8, max_plies=1)
     a = Emu.engine(cfg, blobs[0], 3, 0, 8, nodes_per_game=40)
     b = Emu.engine(cfg, blobs[1], 3, 1, 8)
-    m = EmuMatch(a, b)
+    m = Emu.match(a, b)
     m.start([1, 0, 1], C.playout_positions(5, 3, 24), 8, 8)
     for it in range(400):
         a.step(2)

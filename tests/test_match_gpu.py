@@ -1,7 +1,7 @@
 """GPU: the device hand-off between two engines (include/raz.h raz_match_*, engine.DeviceMatch) and what is built on it -
 EvaluateWorker(handoff="device"), self_opt.start(evaluate=True) - against the host route, an independent host driver and the golden
-games of the unmodified reference's evaluator.  The cases are tests/match_cases.py's; the wave emulator runs them in
-tests/test_match_emu.py."""
+games of the unmodified reference's evaluator.  The cases and the guarded harness around DeviceMatch are tests/match_cases.py's; the
+wave emulator runs them through the same product wrappers in tests/test_match_emu.py."""
 import hashlib
 import logging
 import os
@@ -14,63 +14,15 @@ import match_cases as C
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-GUARD = 4096
+GUARD = C.GUARD
 
 
-class GpuMatch:
-    """engine.DeviceMatch behind the interface of the cases, in a caller's workspace with GUARD bytes of 0x55 behind it."""
-
-    def __init__(self, best, challenger, guard=GUARD):
-        from reversi_alpha_zero_amd._native import lib
-        from reversi_alpha_zero_amd.engine import DeviceMatch
-        need = lib.raz_match_workspace_bytes(best.n_games)
-        self.mem = torch.full((need + 256 + guard,), 0x55, dtype=torch.uint8, device=DEV)
-        self.m = DeviceMatch(best, challenger, workspace=self.mem)
-        self.off, self.need = self.m.workspace_base - self.mem.data_ptr(), need
-
-    def start(self, best_is_black, positions, sims_best, sims_challenger, enable_resign=True):
-        pos = None
-        if positions is not None:
-            u = lambda xs: torch.from_numpy(np.array(xs, dtype=np.uint64).view(np.int64)).to(DEV)
-            pos = (u([p[0] for p in positions]), u([p[1] for p in positions]), torch.tensor([p[2] for p in positions], dtype=torch.uint8, device=DEV))
-        self.m.start(torch.tensor([int(b) for b in best_is_black], dtype=torch.uint8, device=DEV), pos, sims_best, sims_challenger, enable_resign)
-
-    def turn(self):
-        self.m.turn()
-
-    def stats(self):
-        return self.m.stats(raise_on_error=False)
-
-    def read(self):
-        return self.m.read()
-
-    def workspace(self):
-        torch.cuda.synchronize()
-        return self.mem[self.off:self.off + self.need].cpu().numpy()
-
-    def check_guard(self):
-        torch.cuda.synchronize()
-        assert bool((self.mem[self.off + self.need:] == 0x55).all()) and bool((self.mem[:self.off] == 0x55).all()), \
-            "the match wrote outside its workspace"
+def _engine(cfg, blob, n, **kw):
+    from reversi_alpha_zero_amd.engine import DeviceNet, SelfPlayEngine
+    return SelfPlayEngine(cfg, DeviceNet(blob, DEV), n, parts=1, single_stream=True, record_root_w=True, **kw)
 
 
-class Gpu:
-    @staticmethod
-    def engine(cfg, blob, n, seed, sims, first_game_id=0, **kw):
-        from reversi_alpha_zero_amd.engine import DeviceNet, SelfPlayEngine
-        e = SelfPlayEngine(cfg, DeviceNet(blob, DEV), n, seed=seed, sims_hint=sims, max_plies=64, parts=1, single_stream=True, **kw)
-        e.start(first_game_id, sims, n_active=0)
-        return e
-
-    @staticmethod
-    def answers(e):
-        from reversi_alpha_zero_amd.engine import PLY_HEADER
-        pk = e.pack_records(0, e.n_games, plies=1)
-        return pk["headers"].cpu().numpy().view(PLY_HEADER).reshape(-1)["action"], pk["root_n"].cpu().numpy().reshape(e.n_games, 64)
-
-    @staticmethod
-    def match(best, challenger, guard=GUARD):
-        return GpuMatch(best, challenger, guard=guard)
+Gpu = C.Adapter(DEV, _engine)   # the device's instance of the cases' backend
 
 
 @pytest.fixture(scope="module")
@@ -170,14 +122,14 @@ def test_match_refusals_and_edges(blobs):
         DeviceMatch(a, idle)
     with pytest.raises(ValueError, match="workspace"):
         DeviceMatch(a, b, workspace=torch.zeros(lib.raz_match_workspace_bytes(65) - 1, dtype=torch.uint8, device=DEV))
-    m = GpuMatch(a, b)
+    m = Gpu.match(a, b)
     bib = torch.tensor([g % 2 for g in range(65)], dtype=torch.uint8, device=DEV)
     with pytest.raises(ValueError, match="CPU"):
-        m.m.start(bib.cpu(), sims_best=8)
+        m.w.start(bib.cpu(), sims_best=8)
     with pytest.raises(ValueError, match="CPU"):
-        m.m.start(bib, positions=(torch.zeros(65, dtype=torch.int64),) * 2 + (torch.ones(65, dtype=torch.uint8),), sims_best=8)
+        m.w.start(bib, positions=(torch.zeros(65, dtype=torch.int64),) * 2 + (torch.ones(65, dtype=torch.uint8),), sims_best=8)
     with pytest.raises(RuntimeError, match="raz_match_start"):
-        m.m.turn()
+        m.w.turn()
     # no decided slot: hand-offs change no byte of the workspace, before any step and with every search under way
     m.start([g % 2 for g in range(65)], C.playout_positions(2, 65, 20), 8, 8)
     before = m.workspace()
@@ -199,7 +151,7 @@ def test_match_ends_on_an_engine_error(blobs):
     from reversi_alpha_zero_amd.engine import DeviceMatch
     cfg = C.engine_cfg(C.mini_config(1))
     a, b = Gpu.engine(cfg, blobs[0], 3, 0, 8, nodes_per_game=40), Gpu.engine(cfg, blobs[1], 3, 1, 8)
-    m = GpuMatch(a, b)
+    m = Gpu.match(a, b)
     m.start([1, 0, 1], C.playout_positions(5, 3, 24), 8, 8)
     for it in range(400):
         a.step(2)
@@ -210,7 +162,7 @@ def test_match_ends_on_an_engine_error(blobs):
             break
     assert st["live"] == 0 and st["searching_best"] == 0 and st["searching_challenger"] == 0 and st["error"] & 1, st
     with pytest.raises(RuntimeError, match="node pool full"):
-        m.m.stats()
+        m.w.stats()
     games = m.read()[0]
     assert (games["searching"] == 0).all() and (games["winner"] == 0).any()
     m.check_guard()

@@ -20,15 +20,14 @@ def lib():
 
 @pytest.fixture(scope="module")
 def probe():
-    emu = emu_util.load()
+    emu = emu_util.backend()
 
     def run(what, in0, in1, out_dtype, out_shape):
         in0 = np.ascontiguousarray(in0)
         in1 = None if in1 is None else np.ascontiguousarray(in1)
         out = np.zeros(out_shape, dtype=out_dtype)
         n = len(in0)
-        emu_util._check(emu, emu.raz_spec_probe(what, in0.ctypes.data, None if in1 is None else in1.ctypes.data, out.ctypes.data, n, None),
-                        "raz_spec_probe")
+        emu.call("raz_spec_probe", what, in0.ctypes.data, None if in1 is None else in1.ctypes.data, out.ctypes.data, n, None)
         return out
     return run
 

@@ -78,7 +78,7 @@ def test_precision_0_through_the_new_entries_is_v1_to_the_byte():
     assert lib.raz_trainer_bytes2(32, 2, 7, 33, 0) == lib.raz_trainer_bytes(32, 2, 7, 33)
     assert lib.raz_trainer_bytes2(32, 2, 7, 33, 1) > lib.raz_trainer_bytes(32, 2, 7, 33)
     net, blobs = tc.make_net(16, 1, 16), []
-    for cls in (emu_util.EmuTrainer, v2.EmuTrainerF32Via2):
+    for cls in (v2.EmuTrainerV1Entry, v2.EmuTrainerF32Via2):
         t = cls(net, 5, l2=tc.L2)
         for step in range(2):
             t.step(*tc.data(), tc.batch_rows(5, salt=step), 1e-2)

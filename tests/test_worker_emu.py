@@ -47,33 +47,14 @@ rc.data_dir = out; rc.play_data_dir = os.path.join(out, "play_data"); rc.self_pl
 rc.force_simulation_num_file = os.path.join(out, ".force-sim"); rc.self_play_game_idx_file = os.path.join(out, ".self-play-game-idx")
 rc.create_directories = lambda: [os.makedirs(d, exist_ok=True) for d in (rc.play_data_dir, rc.self_play_ggf_data_dir)]
 
-class Net:
-    filters = 16
-    def range_ok(self):
-        return True
-
-class Engine:
-    """What play_block_continuous needs of SelfPlayEngine, on the emulated kernels (a new engine per block: built from the config,
-    it plays under the threshold the block was started with, as raz_engine_set_resign_threshold makes the device engine do)."""
-    def __init__(self, worker, sims):
-        self.e = EmuEngine(worker.config, worker.net_blob, worker.games_in_flight, seed=worker.seed, sims_hint=sims, record_root_w=False)
-    def play_continuous(self, first, total, sims_of, chunk=64, on_chunk=None):
-        ob = self.e.play_continuous(first, total, sims_of(first) if callable(sims_of) else int(sims_of[0]), chunk=8)   # (the worker passes one entry per id)
-        assert ob["done"].all()
-        out = {{k: torch.from_numpy(ob[k]) for k in ("headers", "root_n", "summary")}}
-        if on_chunk is not None:   # streamed emission (one rank): the worker's poll callback sees the outbox fill up - half of it, then all
-            for p in (total // 2, total):
-                done = torch.zeros(total, dtype=torch.uint8)
-                done[:p] = 1
-                if p < total:
-                    done[min(total - 1, p + 1)] = 1   # (a game beyond the first open one has finished too: it must wait)
-                on_chunk(0, int(done.sum()), {{}}, dict(out, done=done))
-        return out, {{"gc_runs": self.e.gc_runs}}
-
 class EmuWorker(BatchedSelfPlayWorker):
     def _get_engine(self, max_sims):
-        self._net = Net()
-        return Engine(self, max_sims)
+        """The product's engine on the emulator's backend, so that the worker drives the real play_continuous (its per-id tables, its
+        polls, its on_chunk).  A new engine per block: built from the config, it plays under the threshold the block was started
+        with, as raz_engine_set_resign_threshold makes the device engine do."""
+        e = EmuEngine(self.config, self.net_blob, self.games_in_flight, seed=self.seed, sims_hint=max_sims, record_root_w=False)
+        self._net = e.net
+        return e
 
 w = EmuWorker(cfg, golden_net_blob(gold["net"]), games_in_flight={slots}, seed=21, device="cpu", rank=rank, world=world,
               block_games={block}, emission={emission!r})

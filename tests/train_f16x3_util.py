@@ -1,5 +1,5 @@
 """Trainer factories of raznet-train-v2 (precision "f16x3": csrc/raz_train_f16x3.h) for the scenarios of tests/train_cases.py: on the
-wave emulator (EmuTrainerF16x3, the `...2` entries with precision 1 on host memory) and on the device
+wave emulator (EmuTrainerF16x3: DeviceTrainer(precision="f16x3") on the emulator's backend) and on the device
 (DeviceTrainer(precision="f16x3")).  The records they write carry the drivers "emu-f16x3" / "gpu-f16x3"."""
 import ctypes
 
@@ -12,34 +12,26 @@ RAZ_TRAIN_F32, RAZ_TRAIN_F16X3 = 0, 1
 
 
 class EmuTrainerF16x3(emu_util.EmuTrainer):
-    """emu_util.EmuTrainer created through raz_trainer_bytes2 / raz_trainer_create2; every other entry is the same."""
-    PRECISION = RAZ_TRAIN_F16X3
+    """emu_util.EmuTrainer at precision "f16x3": DeviceTrainer's own constructor, raz_trainer_bytes2 / raz_trainer_create2."""
 
     def __init__(self, net, max_batch, l2=1e-4):
-        import torch
-        from reversi_alpha_zero_amd.agent.model import ReversiNet
-        from reversi_alpha_zero_amd.agent.trainer import check_trainable
-        check_trainable(net)
-        self.lib = lib = emu_util.load_train()
-        self.device, self.l2, self.max_batch = torch.device("cpu"), float(l2), int(max_batch)
-        self.F, self.R, self.V = net.filters, net.res_layers, net.value_fc
+        super().__init__(net, max_batch, l2=l2, precision="f16x3")
+
+
+EmuTrainerF32Via2 = emu_util.EmuTrainer   # precision 0 through the `...2` entries (what raz_trainer_create makes)
+
+
+class EmuTrainerV1Entry(emu_util.EmuTrainer):
+    """The trainer made again in its workspace by raz_trainer_create, the entry without a precision; every other entry is the same."""
+
+    def __init__(self, net, max_batch, l2=1e-4):
+        super().__init__(net, max_batch, l2=l2)
+        self.close()
         self.handle = ctypes.c_void_p()
-        nbytes = lib.raz_trainer_bytes2(self.F, self.R, self.V, self.max_batch, self.PRECISION)
-        if not nbytes:
-            raise ValueError(f"raz_trainer_bytes2 refuses {self.F}x{self.R}x{self.V}, max_batch {self.max_batch}")
-        self.state_floats = lib.raz_trainer_state_bytes(self.F, self.R, self.V) // 4
-        self.workspace, base = emu_util.aligned(nbytes)
-        emu_util._check(lib, lib.raz_trainer_create2(self.F, self.R, self.V, self.max_batch, self.PRECISION, base, nbytes,
-                                                     ctypes.byref(self.handle), None), "raz_trainer_create2")
-        self.losses = np.zeros(2, dtype=np.float32)
-        self._shape_net = ReversiNet(self.F, self.R, self.V)
-        self.last_batch = 0
+        assert self.workspace.numel() == self.lib.raz_trainer_bytes(self.F, self.R, self.V, self.max_batch)
+        self._launch("raz_trainer_create", self.F, self.R, self.V, self.max_batch, self.workspace.data_ptr(), self.workspace.numel(),
+                     ctypes.byref(self.handle))
         self.from_net(net)
-
-
-class EmuTrainerF32Via2(EmuTrainerF16x3):
-    """Precision 0 through the `...2` entries (what raz_trainer_create makes)."""
-    PRECISION = RAZ_TRAIN_F32
 
 
 class _EmuRaw:
