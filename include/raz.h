@@ -462,6 +462,42 @@ size_t raz_solve_batch_workspace_bytes(size_t n, int max_empties);
 int raz_solve_batch(const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player, size_t n, int exactly,
                     int8_t* d_move, int8_t* d_score, uint8_t* d_status, void* d_workspace, size_t workspace_bytes,
                     uint32_t tuning, raz_stream_t stream);
+/* ---- the exact solver with bounds passed down (csrc/raz_solver_exact.hip) ---------------------------------------------------------
+ * raz_solve_batch(..., exactly = 1, ...) for positions of up to RAZ_SOLVE_EXACT_MAX_EMPTIES empty squares: row i answers exactly what
+ * raz_solve_batch answers in its full-scan mode for every row both accept - the game-theoretic disc difference from the side to
+ * move's view, and the lowest-numbered legal move that attains it - found by a depth-first search that passes bounds down
+ * (alpha-beta) instead of the exhaustive scan.  Status codes 0 / 1 / 2 / 3, d_move = -1 and d_score = -100 where status != 0, as
+ * above; status 2 (refused) now means more than RAZ_SOLVE_EXACT_MAX_EMPTIES empties.  There is no win/loss mode here.  A row's three
+ * bytes are a function of its position alone: the other rows, n, the workspace's size, `tuning` and the stream change no output byte.
+ * d_workspace: 256-byte aligned, at least raz_solve_exact_workspace_bytes(n, e) bytes where e >= the most empties of a searched row
+ * (0 is returned for e > RAZ_SOLVE_EXACT_MAX_EMPTIES and for n > 2^31: refused).  That size holds the default split of one row and
+ * the parked stacks of the lanes that search; with more, more rows share a pass.  After the call its first 8 bytes hold the call's
+ * node visits (moves played), as a uint64 - a number that, unlike the outputs, depends on the order in which lanes finish.
+ * The search runs in ROUNDS: in one launch no lane visits more than the node budget; a lane that runs out parks its stack in the
+ * workspace and resumes in the next launch.  The host ends the rounds when the device reports nothing left, and returns
+ * RAZ_EDEVICE if that has not happened after the number of rounds the bound on the chunk's node visits allows, or as soon as a
+ * group of rounds neither visited a node nor drew a record.
+ * tuning: 0 = the defaults; tests force the partition of the work with
+ *   bits 0-4    leaf size: during the split plies a node with more empties gets its children as tasks (0 = 10; 2..17);
+ *   bits 5-7    the most plies the leaf size is applied for, + 1 (0 = all 6; 1 = none ... 7 = 6 plies).  Below those plies a node
+ *               is split only while it has more than 12 empty squares: that much splitting is not a knob - under every tuning one
+ *               lane's task is a subtree of at most 12 empties;
+ *   bits 8-19   the most rows per chunk (0 = as many as the workspace holds);
+ *   bits 20-23  the node budget of a lane per launch: 0 = 32 768, 1 = 3, 2 = 16, 3 = 128, 4 = 1 024, 5 = 8 192;
+ *   bit 24      children are searched in ascending order (no ordering by the opponent's mobility);
+ *   bit 25      tasks do not share their parent's bound (every task is searched under the full window);
+ * any other bit, or a value outside those ranges: RAZ_EINVAL.
+ * RAZ_EINVAL and NO launch: unknown tuning, a NULL or misaligned array, a workspace below raz_solve_exact_workspace_bytes(n, 0).
+ * RAZ_EINVAL with no output byte written: a workspace below raz_solve_exact_workspace_bytes(n, the most empties of a searched row);
+ * as with raz_solve_batch this one comes after the classification pass.  RAZ_ENOMEM: no host memory for n bytes.
+ * n == 0: RAZ_OK, no launch.  No GPU: RAZ_EDEVICE.
+ * The call SYNCHRONISES `stream` once after the classification pass and once after every GROUP of rounds of every chunk (1, 2, 4 ... 16
+ * launches; the host reads whether anything is left), and is therefore not graph-capturable; when it returns, the outputs are enqueued on `stream`. */
+#define RAZ_SOLVE_EXACT_MAX_EMPTIES 17
+size_t raz_solve_exact_workspace_bytes(size_t n, int max_empties);
+int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player, size_t n, int8_t* d_move,
+                    int8_t* d_score, uint8_t* d_status, void* d_workspace, size_t workspace_bytes, uint32_t tuning,
+                    raz_stream_t stream);
 /* Diagnostics (no reference counterpart): `bytes` at `offset` of one of the engine's device arrays (raz_engine_device_ptr's numbering:
  * 3 the games' control blocks, 6 the solver blocks, 7 / 8 / 9 the solver pool's lane state / headers / active list) copied to host
  * memory.  RAZ_EINVAL when offset + bytes reaches beyond the array.  Synchronises the device. */

@@ -10,6 +10,7 @@ from ..agent.player import effective_play_config
 from ..engine import (ANALYSIS_ENTRY_END, ANALYSIS_ENTRY_PASS, ANALYSIS_MAX_MOVES, EVAL_SOLVED, POS_OVER, POS_PASS_ENTRY, POS_SEARCH,
                       DeviceAnalysis, DeviceNet, SelfPlayEngine)
 from .ggf import convert_to_bitboard_and_actions, parse_ggf
+from .reversi_solver import EXACT_MAX_EMPTIES
 
 logger = getLogger(__name__)
 
@@ -55,12 +56,68 @@ def positions_of(pos, evals):
     return out
 
 
+
+
+def _empties(d):
+    return 64 - bin(d["black"] | d["white"]).count("1")
+
+
+def annotate_exact(games, exact_empties, solver, device="cuda:0"):
+    """Adds the exact solver's verdicts to analyze()'s dictionaries, in place: every position of state `search` or `pass_entry` with
+    at most `exact_empties` empty squares goes through ONE solver.solve_exact_batch call.  Such a position gets solved_move and
+    solved_score (the side to move's view) and, where a move was played, played_score - the exact value of that move: the next
+    position's solved_score, negated when the mover changed, or the final disc difference seen from the mover - and
+    played_loss = solved_score - played_score >= 0.  A pass entry whose side to move cannot move takes the position's after it."""
+    import torch
+    if not (isinstance(exact_empties, int) and 1 <= exact_empties <= EXACT_MAX_EMPTIES):
+        raise ValueError(f"exact_empties must be 1..{EXACT_MAX_EMPTIES}, not {exact_empties!r}")
+    rows = [(g, i) for g, game in enumerate(games) for i, d in enumerate(game)
+            if d["state"] in ("search", "pass_entry") and _empties(d) <= exact_empties]
+    if not rows:
+        return games
+    u = lambda xs: torch.from_numpy(np.array(xs, dtype=np.uint64).view(np.int64)).to(device)   # noqa: E731
+    move, score, status = solver.solve_exact_batch(u([games[g][i]["black"] for g, i in rows]), u([games[g][i]["white"] for g, i in rows]),
+                                                   torch.tensor([games[g][i]["player"] for g, i in rows], dtype=torch.uint8, device=device))
+    move, score, status = (np.asarray(t.cpu()) for t in (move, score, status))
+    must_pass = set()
+    for k, (g, i) in enumerate(rows):
+        if status[k] == 0:
+            games[g][i].update(solved_move=int(move[k]), solved_score=int(score[k]))
+        elif status[k] == 1:
+            must_pass.add((g, i))
+        else:
+            raise ValueError(f"game {g}, position {i}: the exact solver answered status {int(status[k])}")
+
+    def value(game, i, player):
+        """The exact value of position i of the game, seen from `player`; None where it is not known."""
+        if i >= len(game):
+            return None
+        d = game[i]
+        v = d.get("disc_diff") if d["state"] == "over" else d.get("solved_score")
+        return None if v is None else (v if d["player"] == player else -v)
+
+    for g, game in enumerate(games):
+        for i in range(len(game) - 1, -1, -1):   # backwards: a position's successor is finished first
+            d = game[i]
+            if (g, i) in must_pass:
+                v = value(game, i + 1, d["player"])
+                if v is not None:
+                    d.update(solved_move=None, solved_score=v)
+            if "solved_score" in d and d["played"] is not None:
+                v = value(game, i + 1, d["player"])
+                if v is not None:
+                    d.update(played_score=v, played_loss=d["solved_score"] - v)
+    return games
+
+
 class GameAnalyzer:
     """analyze(games): per game a list of per-position dictionaries - moves_made, player (side to move), eval (the most visited
     move's value, from the side to move's view), best_move, visits, top; played_eval / played_diff for the move that was played;
-    exact where the end-game solver answered."""
+    exact where the end-game solver answered.  analyze(games, exact_empties=k) adds annotate_exact's fields for the positions of
+    at most k empty squares (`solver`: the object whose solve_exact_batch answers them; None = a ReversiSolver, built when first needed)."""
 
-    def __init__(self, config, model, play_config=None, slots=1024, device="cuda:0", seed=0):
+    def __init__(self, config, model, play_config=None, slots=1024, device="cuda:0", seed=0, solver=None):
+        self.solver = solver
         self.config, self.device, self.slots, self.seed = config, device, int(slots), seed
         self.play_config = effective_play_config(config, play_config)
         m = getattr(model, "model", model)
@@ -81,8 +138,10 @@ class GameAnalyzer:
         if eng.pool_nearly_full(st, STEPS_PER_COLLECT * COLLECTS_PER_STATS):
             eng.gc(threshold=min(int(eng.cfg.nodes_per_game) // 4, st["max_pool_used"] // 2))
 
-    def analyze(self, games):
+    def analyze(self, games, exact_empties=None):
         import torch
+        if exact_empties is not None and not (isinstance(exact_empties, int) and 1 <= exact_empties <= EXACT_MAX_EMPTIES):
+            raise ValueError(f"exact_empties must be 1..{EXACT_MAX_EMPTIES}, not {exact_empties!r}")
         games = [game_from_ggf(g) if isinstance(g, str) else tuple(g) for g in games]
         if not games:
             return []
@@ -116,4 +175,9 @@ class GameAnalyzer:
             _, p, e = an.results()
             out += [positions_of(p[i], e[i]) for i in range(len(chunk))]
             self.passes += 1
+        if exact_empties is not None:
+            if self.solver is None:
+                from .reversi_solver import ReversiSolver
+                self.solver = ReversiSolver(self.device)
+            annotate_exact(out, exact_empties, self.solver, self.device)
         return out

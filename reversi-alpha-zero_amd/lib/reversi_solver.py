@@ -8,11 +8,26 @@ from .._native import lib, check, tensor_ptr, current_stream_ptr
 
 MAX_EMPTIES = 14   # the library's declared limit: below turn 46 the reference leans on its 30 s wall-clock time-out
 
+EXACT_MAX_EMPTIES = 17   # raz_solve_exact's limit (RAZ_SOLVE_EXACT_MAX_EMPTIES): the full scan's answer, found with bounds passed down
+
 SOLVED, NO_MOVE, TOO_MANY_EMPTIES, NOT_A_POSITION = 0, 1, 2, 3
 
 
 def _player_byte(p):
     return int(getattr(p, "value", p))   # a Player (env/reversi_env.py) or 1 / 2
+
+
+def _popcount64(x):
+    """Set bits per element of an int64 / uint64 device tensor, as an int64 tensor."""
+    import torch
+    x = x.view(torch.int64).reshape(-1)
+    count = torch.zeros_like(x)
+    for shift in range(0, 64, 8):
+        byte = (x >> shift) & 0xff
+        byte = (byte & 0x55) + ((byte >> 1) & 0x55)
+        byte = (byte & 0x33) + ((byte >> 2) & 0x33)
+        count += (byte & 0x0f) + ((byte >> 4) & 0x0f)
+    return count
 
 
 class ReversiSolver:
@@ -24,6 +39,7 @@ class ReversiSolver:
     def __init__(self, device=None):
         self._device = device
         self._ws = None   # the workspace of raz_solve_batch: owned here, grown when a batch needs more, reused otherwise
+        self._ws_exact = None   # the workspace of raz_solve_exact, likewise
 
     def _workspace(self, n, device):
         import torch
@@ -44,16 +60,7 @@ class ReversiSolver:
         colours, a player byte other than 1 / 2); move = -1 and score = -100 where status != 0.  An answer depends on its
         position and the mode alone, never on the rest of the batch."""
         import torch
-        for t in (black, white):
-            if t.dtype not in (torch.int64, torch.uint64):
-                raise TypeError("bitboard tensors must be int64/uint64")
-        if next_player.dtype != torch.uint8:
-            raise TypeError("next_player must be a uint8 tensor")
-        if not (black.is_cuda and white.is_cuda and next_player.is_cuda):
-            raise ValueError("solve_batch is device-only (no CPU fallback)")
-        n = black.numel()
-        if white.numel() != n or next_player.numel() != n:
-            raise ValueError("black, white and next_player must have the same number of elements")
+        n = self._check_batch(black, white, next_player, "solve_batch")
         move = torch.empty(n, dtype=torch.int8, device=black.device)
         score = torch.empty(n, dtype=torch.int8, device=black.device)
         status = torch.empty(n, dtype=torch.uint8, device=black.device)
@@ -63,6 +70,66 @@ class ReversiSolver:
                                       tensor_ptr(move), tensor_ptr(score), tensor_ptr(status), tensor_ptr(ws), ws.numel(), 0,
                                       current_stream_ptr()), "raz_solve_batch")
         return move, score, status
+
+    @staticmethod
+    def _check_batch(black, white, next_player, what):
+        import torch
+        for t in (black, white):
+            if t.dtype not in (torch.int64, torch.uint64):
+                raise TypeError("bitboard tensors must be int64/uint64")
+        if next_player.dtype != torch.uint8:
+            raise TypeError("next_player must be a uint8 tensor")
+        if not (black.is_cuda and white.is_cuda and next_player.is_cuda):
+            raise ValueError(f"{what} is device-only (no CPU fallback)")
+        n = black.numel()
+        if white.numel() != n or next_player.numel() != n:
+            raise ValueError("black, white and next_player must have the same number of elements")
+        return n
+
+    def solve_exact_batch(self, black, white, next_player):
+        """solve_batch(..., exactly=True) for positions of up to EXACT_MAX_EMPTIES empty squares (raz_solve_exact: the same
+        answers, found by a search that passes bounds down): device tensors (move int8, score int8, status uint8); status 2 =
+        more than EXACT_MAX_EMPTIES empties.  The call synchronises the current stream (once per group of rounds of the search)."""
+        import torch
+        n = self._check_batch(black, white, next_player, "solve_exact_batch")
+        move = torch.empty(n, dtype=torch.int8, device=black.device)
+        score = torch.empty(n, dtype=torch.int8, device=black.device)
+        status = torch.empty(n, dtype=torch.uint8, device=black.device)
+        if n:
+            empties = 64 - _popcount64(black.view(torch.int64).reshape(-1) | white.view(torch.int64).reshape(-1))
+            deepest = int(torch.where(empties <= EXACT_MAX_EMPTIES, empties, torch.zeros_like(empties)).max())
+            want = lib.raz_solve_exact_workspace_bytes(n, deepest)
+            if want == 0:
+                raise ValueError(f"raz_solve_exact refuses a batch of {n} positions")
+            want += min(n * 65536, 1 << 31)   # room for whole rows to share a pass
+            ws = self._ws_exact
+            if ws is None or ws.numel() < want or ws.device != black.device:
+                ws = self._ws_exact = torch.empty(want, dtype=torch.uint8, device=black.device)
+            check(lib.raz_solve_exact(tensor_ptr(black), tensor_ptr(white), tensor_ptr(next_player), n, tensor_ptr(move),
+                                      tensor_ptr(score), tensor_ptr(status), tensor_ptr(ws), ws.numel(), 0, current_stream_ptr()),
+                  "raz_solve_exact")
+        return move, score, status
+
+    def solve_exact(self, black, white, next_player):
+        """solve(..., exactly=True) for a position of up to EXACT_MAX_EMPTIES empty squares: (move, score) or (None, None)."""
+        import torch
+        device = torch.device(self._device or "cuda")
+        player = _player_byte(next_player)
+        if player not in (1, 2):
+            raise ValueError(f"next_player must be Player.black / Player.white or 1 / 2, not {next_player!r}")
+        m64 = (1 << 64) - 1
+        b = torch.from_numpy(np.array([int(black) & m64], dtype=np.uint64).view(np.int64)).to(device)
+        w = torch.from_numpy(np.array([int(white) & m64], dtype=np.uint64).view(np.int64)).to(device)
+        p = torch.tensor([player], dtype=torch.uint8, device=device)
+        move, score, status = (int(t.cpu()[0]) for t in self.solve_exact_batch(b, w, p))
+        if status == TOO_MANY_EMPTIES:
+            raise ValueError(f"the exact solver takes positions of at most {EXACT_MAX_EMPTIES} empty squares "
+                             f"(this one has {64 - bin((int(black) | int(white)) & m64).count('1')})")
+        if status == NOT_A_POSITION:
+            raise ValueError("not a position: a square holds a disc of both colours")
+        if status == NO_MOVE:
+            return None, None
+        return move, score
 
     def solve(self, black, white, next_player, timeout=30, exactly=False):
         """ReversiSolver.solve (lib/alt/reversi_solver_cython.pyx:40-61): (move, score) with score the disc difference from the
