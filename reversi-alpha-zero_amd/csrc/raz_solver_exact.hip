@@ -3,19 +3,16 @@
 // exhaustive scan of raz_solver_batch.hip.  The answer - the game-theoretic disc difference and the lowest-numbered move that
 // attains it - is the same pure function of the position; only the number of nodes visited differs.
 //
-//   k_se_classify  one thread per row: status / empties, into the workspace (no output byte yet); the host cuts chunks;
-//   k_se_roots     one RECORD per row of the chunk (the position from its mover's view);
-//   k_se_expand    ply by ply, for at most `plies` plies: a record of more than `leaf` empties gets its children as one run of
-//                  records in ASCENDING move order.  Every record knows its parent and carries a BOUND word: the best value a
-//                  finished child has proven for it so far;
+//   the split      raz_solver_split.h's kernels, shared with raz_solver_batch.hip: classify, roots, expand ply by ply (a record of
+//                  more than 12 empties and, for at most `plies` plies, one of more than `leaf`).  Here every record knows its
+//                  parent and carries a BOUND word: the best value a finished child has proven for it so far;
 //   k_se_search    one task per LANE: a record that was not expanded is searched depth first, fail-soft, children ordered by the
 //                  opponent's mobility (three tiers; not below SE_ORDER_MIN empties), the last empty square finished in
 //                  solver_play.  The ancestors' frames live in the workspace ([level][word][slot]: coalesced), and so does the
 //                  node itself between launches: a lane that has visited `budget` nodes in this launch PARKS - its registers go
 //                  to its slot - and the same slot resumes in the next launch.  A wave draws tasks for its idle lanes with one
-//                  atomicAdd, as k_sb_leaves does;
-//   k_se_fold      level by level, bottom up: solver_scan (ascending, strict improvement) over the children's results;
-//   k_se_out       the chunk's rows of d_move / d_score / d_status.
+//                  atomicAdd, as k_sb_leaves does (solver_draw);
+//   the fold and the output rows, raz_solver_split.h's again.
 //
 // Sibling bounds.  A task T whose parent P has the bound a (P's view: v(P) >= a, proven by a finished sibling) is searched under a
 // window ONE WIDER than alpha-beta's: T's result is exact whenever T's value in P's view is >= a, and otherwise a bound that says
@@ -28,10 +25,7 @@
 // Every launch ends: a lane stops at `budget` visits, and a round advances every parked task by at least one node (its lane
 // resumes it before it may draw another).  The host loop runs until the device reports no parked lane and no undrawn record, under
 // a cap on rounds derived from the bound on the chunk's node visits.  No floating point, no memo.
-#include <exception>
-#include <vector>
-#include "raz_internal.h"
-#include "raz_solver_search.h"   // solver_play (the move function, the pass rule, the end of the game), solver_scan
+#include "raz_solver_split.h"
 
 namespace {
 
@@ -42,133 +36,35 @@ namespace {
 #define SE_ORDER_MIN 5        // nodes with fewer empties play their moves in ascending order
 #define SE_DEFAULT_BUDGET 32768u
 #define SE_FRAMES 16          // a node has at least two empties: a task of e <= 17 empties pushes at most e - 2 frames
-#define SE_UNKNOWN RAZ_SOLVER_UNKNOWN
-#define SE_HDR_BYTES 256
 #define SE_REC_BYTES 32
 #define SE_SLOT_W64 (SE_FRAMES * 5 + 5)
 #define SE_SLOT_W32 (SE_FRAMES + 3)
 #define SE_SLOT_BYTES (SE_SLOT_W64 * 8 + SE_SLOT_W32 * 4)
 #define SE_MAX_SLOTS 131072u
-#define SE_NONE 0xffffffffu
-#define SE_LO (-66)           // below every value
+#define SE_NONE SPLIT_NONE
+#define SE_LO SPLIT_LOWEST    // below every value
 #define SE_HI 66              // above every value
 #define SE_TUNING_MASK 0x03ffffffu
 static_assert(SE_MAX_EMPTIES - 2 <= SE_FRAMES, "frames");
+static_assert(SE_MAX_PLIES + 2 <= SPLIT_LEVELS, "levels");
 static_assert(RAZ_SOLVER_INLINE_LAST >= 1, "SE_FRAMES rests on solver_play finishing the last empty square itself");
 
-#define SE_ROW_NO_MOVE 0xF1
-#define SE_ROW_TOO_DEEP 0xF2
-#define SE_ROW_INVALID 0xF3
-
-struct SeHdr {
-    unsigned long long visits;   // [0]  node visits of the call
-    uint32_t count;              // [8]  records in use
-    uint32_t next;               // [12] next record to look at
-    uint32_t open;               // [16] lanes that parked a task in the last launch
-    uint32_t overflow;           // [20] a run of children did not fit (the host's sizing was wrong): the call fails
-    uint32_t level[SE_MAX_PLIES + 2];
-};
-static_assert(sizeof(SeHdr) <= SE_HDR_BYTES, "header");
-
-// a record's meta word is raz_solver_batch.hip's: bits 0-7 value + 128 (0 = not known yet), 8-15 best move + 1, 16-17 kind (0 a
-// value known at once, 1 the parent's value is -f, 2 it is +f: a pass, or a root), 18 expanded, 19-23 children
-struct SeWs {
-    SeHdr* hdr;
-    uint8_t* emp;
-    unsigned long long *own, *enemy;
-    uint32_t *first, *meta, *parent, *bound;   // bound: value + 128 of the best finished child (this record's view)
+struct SeWs : SplitWs {
+    static constexpr int kMaxEmpties = SE_MAX_EMPTIES, kAlways = SE_MAX_TASK;
+    static constexpr bool kLinks = true;
+    static constexpr const char* kWho = "raz_solve_exact";
+    static constexpr auto kBytes = raz_solve_exact_workspace_bytes;
+    uint32_t *parent, *bound;   // per record: its parent (SE_NONE: a root); value + 128 of the best finished child (this record's view)
     uint32_t cap;
-    unsigned long long* s64;   // slots: word j of slot s = s64[j * nslots + s]
+    unsigned long long* s64;    // slots: word j of slot s = s64[j * nslots + s]
     uint32_t* s32;
     uint32_t nslots;
 };
-__device__ __forceinline__ uint32_t se_meta(int value, int move, int kind, int expanded, int nch) {
-    return (uint32_t)(value + 128) | ((uint32_t)(move + 1) << 8) | ((uint32_t)kind << 16) | ((uint32_t)expanded << 18) | ((uint32_t)nch << 19);
-}
-__device__ __forceinline__ int se_value(uint32_t m) { return (int)(m & 0xffu) - 128; }
-__device__ __forceinline__ int se_kind(uint32_t m) { return (int)((m >> 16) & 3u); }
 
-constexpr int kBlock = 256;
-
-__global__ __launch_bounds__(kBlock) void k_se_classify(SeWs W, const unsigned long long* __restrict__ black, const unsigned long long* __restrict__ white,
-                                                        const uint8_t* __restrict__ player, size_t n) {
-    const size_t stride = (size_t)gridDim.x * kBlock;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const raz_bb b = black[i], w = white[i];
-        const int p = player[i];
-        int code;
-        if ((b & w) || (p != 1 && p != 2)) code = SE_ROW_INVALID;
-        else if (bb_popcount(~(b | w)) > SE_MAX_EMPTIES) code = SE_ROW_TOO_DEEP;
-        else if (!bbv_legal_moves(p == 1 ? b : w, p == 1 ? w : b)) code = SE_ROW_NO_MOVE;
-        else code = bb_popcount(~(b | w));
-        W.emp[i] = (uint8_t)code;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_se_roots(SeWs W, const unsigned long long* __restrict__ black, const unsigned long long* __restrict__ white,
-                                                     const uint8_t* __restrict__ player, size_t r0, uint32_t rows, uint32_t slots) {
+// before a chunk's first round: no slot holds a task
+__global__ __launch_bounds__(kBlock) void k_se_clear_slots(SeWs W, uint32_t slots) {
     const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < rows; i += stride) {
-        const bool search = W.emp[r0 + i] <= SE_MAX_EMPTIES;
-        const bool is_black = player[r0 + i] == 1;
-        W.own[i] = search ? (is_black ? black[r0 + i] : white[r0 + i]) : 0ULL;
-        W.enemy[i] = search ? (is_black ? white[r0 + i] : black[r0 + i]) : 0ULL;
-        W.first[i] = 0u;
-        W.parent[i] = SE_NONE;
-        W.bound[i] = (uint32_t)(SE_LO + 128);
-        W.meta[i] = search ? se_meta(SE_UNKNOWN, -1, 2, 0, 0) : se_meta(-100, -1, 0, 0, 0);
-    }
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < slots; i += stride) W.s32[(size_t)(SE_FRAMES + 1) * W.nslots + i] = SE_NONE;   // no slot holds a task
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        W.hdr->count = rows;
-        W.hdr->next = 0u;
-        W.hdr->open = 0u;
-        W.hdr->overflow = 0u;
-        W.hdr->level[0] = 0u;
-        W.hdr->level[1] = rows;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_se_mark(SeWs W, int p) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) W.hdr->level[p + 2] = W.hdr->count;
-}
-
-// a record of level p is expanded when it has more than SE_MAX_TASK empties (not a knob), or more than `leaf` and p < plies
-__global__ __launch_bounds__(kBlock) void k_se_expand(SeWs W, int p, int leaf, int plies) {
-    const uint32_t lo = W.hdr->level[p], hi = W.hdr->level[p + 1], stride = gridDim.x * kBlock;
-    uint32_t visits = 0u;
-    for (uint32_t i = lo + blockIdx.x * kBlock + threadIdx.x; i < hi; i += stride) {
-        const uint32_t m = W.meta[i];
-        if (se_kind(m) == 0) continue;
-        const raz_bb own = W.own[i], enemy = W.enemy[i];
-        const int e = bb_popcount(~(own | enemy));
-        if (!(e > SE_MAX_TASK || (e > leaf && p < plies))) continue;
-        const raz_bb moves = bbv_legal_moves(own, enemy);
-        const int nch = bb_popcount(moves);
-        const uint32_t first = atomicAdd(&W.hdr->count, (uint32_t)nch);
-        // (the host sizes the chunks by se_need, so a run always fits; if one ever did not, nothing is stored and the header says
-        // so: the host ends the call with an error before any record is searched)
-        if (first + (uint32_t)nch > W.cap || first + (uint32_t)nch < first) {
-            W.hdr->overflow = 1u;
-            continue;
-        }
-        uint32_t c = first;
-        for (raz_bb l = moves; l; l &= l - 1, ++c) {
-            raz_bb no, ne, nm;
-            int v;
-            const int kind = solver_play(__ffsll((long long)l) - 1, own, enemy, no, ne, nm, v, true);
-            W.own[c] = no;
-            W.enemy[c] = ne;
-            W.first[c] = 0u;
-            W.parent[c] = i;
-            W.bound[c] = (uint32_t)(SE_LO + 128);
-            W.meta[c] = se_meta(kind ? SE_UNKNOWN : v, -1, kind, 0, 0);
-        }
-        visits += (uint32_t)nch;
-        W.first[i] = first;
-        W.meta[i] = se_meta(SE_UNKNOWN, -1, se_kind(m), 1, nch);
-    }
-    if (visits) atomicAdd(&W.hdr->visits, (unsigned long long)visits);
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < slots; i += stride) W.s32[(size_t)(SE_FRAMES + 1) * W.nslots + i] = SE_NONE;
 }
 
 // the node a lane's search stands on
@@ -278,14 +174,12 @@ __global__ __launch_bounds__(64) void k_se_search(SeWs W, uint32_t budget, uint3
         const unsigned long long wanting = __ballot(!have && visits < budget);
         if (!working && (dry || !wanting)) break;
         if (!dry && wanting && (!working || (it & 7u) == 0u)) {
-            uint32_t base = 0u;
-            if (lane == 0) base = atomicAdd(&W.hdr->next, (uint32_t)__popcll(wanting));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane(base);
+            uint32_t base;
+            const uint32_t t = solver_draw(&W.hdr->next, wanting, lane, base);
             if (base >= total) dry = true;
-            const uint32_t t = base + (uint32_t)__popcll(wanting & ((1ULL << lane) - 1ULL));
             if (!have && visits < budget && t < total) {
                 const uint32_t m = W.meta[t];
-                if (se_kind(m) != 0 && !((m >> 18) & 1u)) {
+                if (rec_kind(m) != 0 && !rec_expanded(m)) {
                     task = t;
                     task_meta = m;
                     const raz_bb own = W.own[t], enemy = W.enemy[t];
@@ -294,7 +188,7 @@ __global__ __launch_bounds__(64) void k_se_search(SeWs W, uint32_t budget, uint3
                     if (siblings && par != SE_NONE) {
                         // the parent's bound pb: exact where this task's value in the parent's view is >= pb
                         const int pb = (int)*(volatile uint32_t*)&W.bound[par] - 128;
-                        if (se_kind(m) == 1) b = 1 - pb;
+                        if (rec_kind(m) == 1) b = 1 - pb;
                         else a = pb - 1;
                     }
                     nd.begin(own, enemy, bbv_legal_moves(own, enemy), a, b, 0, 0, ordered);
@@ -313,8 +207,8 @@ __global__ __launch_bounds__(64) void k_se_search(SeWs W, uint32_t budget, uint3
                 }
                 if (returns == 2) break;
                 if (d == 0) {
-                    const int r = nd.best, kind = se_kind(task_meta);
-                    W.meta[task] = se_meta(kind == 1 ? -r : r, bmv < 64 ? bmv : -1, kind, 0, 0);
+                    const int r = nd.best, kind = rec_kind(task_meta);
+                    W.meta[task] = rec_meta(kind == 1 ? -r : r, bmv < 64 ? bmv : -1, kind, 0, 0);
                     const uint32_t par = W.parent[task];
                     if (siblings && par != SE_NONE) {   // (only a valid lower bound of the parent's value raises its bound)
                         if (kind == 1 && r < nd.beta) se_raise(&W.bound[par], (uint32_t)(-r + 128));
@@ -372,47 +266,7 @@ __global__ __launch_bounds__(64) void k_se_search(SeWs W, uint32_t budget, uint3
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_se_fold(SeWs W, int p) {
-    const uint32_t lo = W.hdr->level[p], hi = W.hdr->level[p + 1], stride = gridDim.x * kBlock;
-    for (uint32_t i = lo + blockIdx.x * kBlock + threadIdx.x; i < hi; i += stride) {
-        const uint32_t m = W.meta[i];
-        if (!((m >> 18) & 1u)) continue;
-        const int nch = (int)((m >> 19) & 31u);
-        const uint32_t first = W.first[i];
-        int bm, bs;
-        solver_scan([&](int j) { return se_value(W.meta[first + j]); }, nch, bbv_legal_moves(W.own[i], W.enemy[i]), true, bm, bs);
-        W.meta[i] = se_meta(se_kind(m) == 1 ? -bs : bs, bm, se_kind(m), 1, nch);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_se_out(SeWs W, size_t r0, uint32_t rows, int8_t* __restrict__ move, int8_t* __restrict__ score,
-                                                   uint8_t* __restrict__ status) {
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < rows; i += stride) {
-        const int code = W.emp[r0 + i];
-        const uint32_t m = W.meta[i];
-        const bool search = code <= SE_MAX_EMPTIES;
-        move[r0 + i] = (int8_t)(search ? (int)((m >> 8) & 0xffu) - 1 : -1);
-        score[r0 + i] = (int8_t)(search ? se_value(m) : -100);
-        status[r0 + i] = (uint8_t)(search ? 0 : code - 0xF0);
-    }
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-int se_plies(int e, int leaf, int plies) {
-    const int asked = e > leaf ? (e - leaf < plies ? e - leaf : plies) : 0, forced = e > SE_MAX_TASK ? e - SE_MAX_TASK : 0;
-    return asked > forced ? asked : forced;
-}
-// the most records a row can need: level k holds at most e (e - 1) ... (e - k + 1) nodes
-size_t se_need(int e, int leaf, int plies) {
-    const int k_max = se_plies(e, leaf, plies);
-    size_t total = 1, level = 1;
-    for (int k = 0; k < k_max; ++k) {
-        level *= (size_t)(e - k);
-        total += level;
-    }
-    return total;
-}
 // a bound on the node visits under a position of e empties, whatever the bounds cut: T(e) = e (1 + T(e - 1)), saturating
 unsigned long long se_tree(int e) {
     unsigned long long t = 0;
@@ -422,12 +276,7 @@ unsigned long long se_tree(int e) {
     }
     return t;
 }
-size_t se_fixed_bytes(size_t n) { return SE_HDR_BYTES + (n + 255) / 256 * 256; }
 size_t se_good_slots(int e) { return e <= 8 ? 4096 : SE_MAX_SLOTS; }
-unsigned se_grid(size_t items, unsigned per, unsigned most) {
-    const size_t g = (items + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : (g > most ? most : g));
-}
 const uint32_t kBudgets[] = {SE_DEFAULT_BUDGET, 3u, 16u, 128u, 1024u, 8192u};
 
 }  // namespace
@@ -435,9 +284,9 @@ const uint32_t kBudgets[] = {SE_DEFAULT_BUDGET, 3u, 16u, 128u, 1024u, 8192u};
 extern "C" size_t raz_solve_exact_workspace_bytes(size_t n, int max_empties) {
     if (max_empties > SE_MAX_EMPTIES || n > ((size_t)1 << 31)) return 0;
     if (max_empties < 0) max_empties = 0;
-    size_t rec = se_need(max_empties, SE_DEFAULT_LEAF, SE_MAX_PLIES);
+    size_t rec = split_need(max_empties, SE_DEFAULT_LEAF, SE_MAX_PLIES, SE_MAX_TASK);
     if (rec < 256) rec = 256;
-    return se_fixed_bytes(n) + (se_good_slots(max_empties) * SE_SLOT_BYTES + 255) / 256 * 256 + rec * SE_REC_BYTES;
+    return split_fixed_bytes(n) + (se_good_slots(max_empties) * SE_SLOT_BYTES + 255) / 256 * 256 + rec * SE_REC_BYTES;
 }
 
 extern "C" int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player, size_t n, int8_t* d_move,
@@ -453,15 +302,9 @@ extern "C" int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white,
     if (budget_code >= sizeof(kBudgets) / sizeof(kBudgets[0])) return raz_fail(RAZ_EINVAL, "raz_solve_exact: tuning: unknown node budget");
     const uint32_t budget = kBudgets[budget_code];
     if (n == 0) return RAZ_OK;
-    if (!d_black || !d_white || !d_player || !d_move || !d_score || !d_status || !d_workspace)
-        return raz_fail(RAZ_EINVAL, "raz_solve_exact: NULL array");
-    if (((uintptr_t)d_black | (uintptr_t)d_white) & 7u) return raz_fail(RAZ_EINVAL, "raz_solve_exact: bitboard arrays must be 8-byte aligned");
-    if ((uintptr_t)d_workspace & 255u) return raz_fail(RAZ_EINVAL, "raz_solve_exact: the workspace must be 256-byte aligned");
-    const size_t least = raz_solve_exact_workspace_bytes(n, 0);
-    if (least == 0) return raz_fail(RAZ_EINVAL, "raz_solve_exact: n too large");
-    if (workspace_bytes < least) return raz_fail(RAZ_EINVAL, "raz_solve_exact: workspace smaller than raz_solve_exact_workspace_bytes(n, 0)");
+    if (int rc = split_check_args<SeWs>(d_black, d_white, d_player, n, d_move, d_score, d_status, d_workspace, workspace_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t fixed = se_fixed_bytes(n), avail = workspace_bytes - fixed;
+    const size_t fixed = split_fixed_bytes(n), avail = workspace_bytes - fixed;
     // the slots take at most a fifth of what is left (and never more than SE_MAX_SLOTS), the records the rest
     size_t nslots = avail / 5 / SE_SLOT_BYTES / 64 * 64;
     if (nslots > SE_MAX_SLOTS) nslots = SE_MAX_SLOTS;
@@ -471,64 +314,36 @@ extern "C" int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white,
     if (cap > 0xfffffff0u) cap = 0xfffffff0u;
     SeWs W;
     unsigned char* base = (unsigned char*)d_workspace;
-    W.hdr = (SeHdr*)base;
-    W.emp = base + SE_HDR_BYTES;
+    split_layout(W, base, base + fixed + slot_bytes, cap);
+    W.parent = W.meta + cap;
+    W.bound = W.parent + cap;
     W.s64 = (unsigned long long*)(base + fixed);
     W.s32 = (uint32_t*)(W.s64 + (size_t)SE_SLOT_W64 * nslots);
     W.nslots = (uint32_t)nslots;
-    W.own = (unsigned long long*)(base + fixed + slot_bytes);
-    W.enemy = W.own + cap;
-    W.first = (uint32_t*)(W.enemy + cap);
-    W.meta = W.first + cap;
-    W.parent = W.meta + cap;
-    W.bound = W.parent + cap;
-    W.cap = (uint32_t)cap;
     const unsigned long long *bl = (const unsigned long long*)d_black, *wh = (const unsigned long long*)d_white;
-
-    RAZ_HIP_TRY(hipMemsetAsync(base, 0, SE_HDR_BYTES, s), "raz_solve_exact (clear)");
-    hipLaunchKernelGGL(k_se_classify, dim3(se_grid(n, kBlock, 2048)), dim3(kBlock), 0, s, W, bl, wh, d_player, n);
-    if (int rc = raz_check_launch("raz_solve_exact (classify)")) return rc;
     std::vector<uint8_t> emp;
-    try {
-        emp.resize(n);
-    } catch (const std::exception&) {
-        return raz_fail(RAZ_ENOMEM, "raz_solve_exact: no host memory for the rows' empties");
-    }
-    RAZ_HIP_TRY(hipMemcpyAsync(emp.data(), W.emp, n, hipMemcpyDeviceToHost, s), "raz_solve_exact (read the rows' empties)");
-    RAZ_HIP_TRY(hipStreamSynchronize(s), "raz_solve_exact (synchronise)");
-    int deepest = 0;
-    for (size_t i = 0; i < n; ++i)
-        if (emp[i] <= SE_MAX_EMPTIES && emp[i] > deepest) deepest = emp[i];
-    if (workspace_bytes < raz_solve_exact_workspace_bytes(n, deepest))   // (no output byte has been written)
-        return raz_fail(RAZ_EINVAL, "raz_solve_exact: workspace smaller than raz_solve_exact_workspace_bytes(n, the most empties of a row)");
+    if (int rc = split_classify(W, bl, wh, d_player, n, workspace_bytes, s, emp)) return rc;
 
     for (size_t r0 = 0; r0 < n;) {
-        // the chunk: as many rows as the records hold in the worst case; where the first row's split does not fit, the chunk splits
-        // fewer plies (no split at all is one record: it always fits)
+        // where the first row's split does not fit the records, the chunk splits fewer plies (no split at all is one record: it
+        // always fits)
         int p_here = plies;
         const int e0 = emp[r0] <= SE_MAX_EMPTIES ? emp[r0] : 0;
-        while (p_here > 0 && se_need(e0, leaf, p_here) > cap) --p_here;
-        size_t used = 0, r1 = r0;
-        int chunk_plies = 0;
+        while (p_here > 0 && split_need(e0, leaf, p_here, SE_MAX_TASK) > cap) --p_here;
+        const SplitChunk c = split_chunk<SeWs>(emp, r0, leaf, p_here, cap, chunk_rows);
         unsigned long long nodes = 0;
-        while (r1 < n && (chunk_rows == 0 || r1 - r0 < chunk_rows)) {
-            const int e = emp[r1] <= SE_MAX_EMPTIES ? emp[r1] : 0;
-            const size_t need = se_need(e, leaf, p_here);
-            if (used + need > cap && r1 > r0) break;
-            used += need;
-            const int k = se_plies(e, leaf, p_here);
-            if (k > chunk_plies) chunk_plies = k;
-            const unsigned long long t = se_tree(e);
+        for (size_t r = r0; r < c.r1; ++r) {
+            const unsigned long long t = se_tree(emp[r] <= SE_MAX_EMPTIES ? emp[r] : 0);
             nodes = nodes + t < (1ULL << 62) ? nodes + t : (1ULL << 62);
-            ++r1;
         }
-        const uint32_t rows = (uint32_t)(r1 - r0);
-        const unsigned blocks = se_grid(used, 64, (unsigned)(nslots / 64));
-        hipLaunchKernelGGL(k_se_roots, dim3(se_grid(rows > blocks * 64u ? rows : blocks * 64u, kBlock, 2048)), dim3(kBlock), 0, s, W, bl, wh, d_player,
-                           r0, rows, blocks * 64u);
-        for (int p = 0; p < chunk_plies; ++p) {
-            hipLaunchKernelGGL(k_se_expand, dim3(se_grid(used, kBlock, 2048)), dim3(kBlock), 0, s, W, p, leaf, p_here);
-            hipLaunchKernelGGL(k_se_mark, dim3(1), dim3(64), 0, s, W, p);
+        const uint32_t rows = (uint32_t)(c.r1 - r0);
+        const size_t used = c.used;
+        const unsigned blocks = split_grid(used, 64, (unsigned)(nslots / 64));
+        hipLaunchKernelGGL(k_split_roots<SeWs>, dim3(split_grid(rows, kBlock, 2048)), dim3(kBlock), 0, s, W, bl, wh, d_player, r0, rows);
+        hipLaunchKernelGGL(k_se_clear_slots, dim3(split_grid(blocks * 64u, kBlock, 2048)), dim3(kBlock), 0, s, W, blocks * 64u);
+        for (int p = 0; p < c.plies; ++p) {
+            hipLaunchKernelGGL(k_split_expand<SeWs>, dim3(split_grid(used, kBlock, 2048)), dim3(kBlock), 0, s, W, p, leaf, p_here, 1u);
+            hipLaunchKernelGGL(k_split_mark<SeWs>, dim3(1), dim3(64), 0, s, W, p);
         }
         if (int rc = raz_check_launch("raz_solve_exact (split)")) return rc;
         // the rounds: every round visits at least min(budget, what is left) nodes on every lane that holds a task, and lanes
@@ -545,8 +360,8 @@ extern "C" int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white,
             RAZ_HIP_TRY(hipMemsetAsync(&W.hdr->open, 0, sizeof(uint32_t), s), "raz_solve_exact (round)");
             for (unsigned k = 0; k < group; ++k) hipLaunchKernelGGL(k_se_search, dim3(blocks), dim3(64), 0, s, W, budget, flags);
             if (int rc = raz_check_launch("raz_solve_exact (search)")) return rc;
-            SeHdr h;
-            RAZ_HIP_TRY(hipMemcpyAsync(&h, W.hdr, sizeof(SeHdr), hipMemcpyDeviceToHost, s), "raz_solve_exact (read the round's state)");
+            SplitHdr h;
+            RAZ_HIP_TRY(hipMemcpyAsync(&h, W.hdr, sizeof(SplitHdr), hipMemcpyDeviceToHost, s), "raz_solve_exact (read the round's state)");
             RAZ_HIP_TRY(hipStreamSynchronize(s), "raz_solve_exact (synchronise)");
             if (h.overflow) return raz_fail(RAZ_EDEVICE, "raz_solve_exact: the split did not fit the records the host had sized for it");
             done = h.open == 0u && h.next >= (h.count < W.cap ? h.count : W.cap);
@@ -557,10 +372,10 @@ extern "C" int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white,
             seen_next = h.next;
         }
         if (!done) return raz_fail(RAZ_EDEVICE, "raz_solve_exact: the search did not end within the rounds its node bound allows");
-        for (int p = chunk_plies - 1; p >= 0; --p) hipLaunchKernelGGL(k_se_fold, dim3(se_grid(used, kBlock, 2048)), dim3(kBlock), 0, s, W, p);
-        hipLaunchKernelGGL(k_se_out, dim3(se_grid(rows, kBlock, 2048)), dim3(kBlock), 0, s, W, r0, rows, d_move, d_score, d_status);
+        for (int p = c.plies - 1; p >= 0; --p) hipLaunchKernelGGL(k_split_fold<SeWs>, dim3(split_grid(used, kBlock, 2048)), dim3(kBlock), 0, s, W, p, 1u);
+        hipLaunchKernelGGL(k_split_out<SeWs>, dim3(split_grid(rows, kBlock, 2048)), dim3(kBlock), 0, s, W, r0, rows, d_move, d_score, d_status);
         if (int rc = raz_check_launch("raz_solve_exact")) return rc;
-        r0 = r1;
+        r0 = c.r1;
     }
     return RAZ_OK;
 }

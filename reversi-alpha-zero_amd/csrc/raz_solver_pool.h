@@ -27,10 +27,11 @@
 // would have skipped is searched as well changes no answer.  Workers never talk to each other inside a launch (only the solves' task
 // counters and the claim of a memo slot are atomic); everything else crosses kernel boundaries.  Measurements: DESIGN.md 4.7.
 // The search a lane runs - what a move leads to, a node's scan over its children's values, the node and its frame word - is stated in
-// raz_solver_search.h, once for this pool and for raz_solve_batch (raz_solver_batch.hip); here are the task tree, the memo, the draws.
+// raz_solver_search.h, once for this pool and for raz_solve_batch (raz_solver_batch.hip; raz_solve_exact takes its move function and
+// scan from there too); here are the task tree, the memo, the draws.
 #pragma once
 #include "raz_engine_core.h"
-#include "raz_solver_search.h"   // the per-lane search itself: solver_play, solver_scan, SolverNode (shared with raz_solver_batch.hip)
+#include "raz_solver_search.h"   // the per-lane search itself: solver_play, solver_scan, SolverNode (shared with raz_solver_batch.hip; raz_solver_split.h)
 
 namespace {
 

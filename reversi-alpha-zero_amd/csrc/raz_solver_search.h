@@ -1,5 +1,7 @@
 // raz_solver_search.h — the reference's end-game recursion (lib/alt/reversi_solver_cython.pyx:40-127) as ONE LANE runs it, stated
 // once for the two solvers whose lanes do: the engine's pool (raz_solver_pool.h) and raz_solve_batch (raz_solver_batch.hip).
+// raz_solve_exact (raz_solver_exact.hip) searches with bounds on a node of its own and takes solver_play and solver_scan from here;
+// the record tree the two batch calls split their rows into, whose kernels run the same two functions, is raz_solver_split.h's.
 // Here are the RULES - what a move leads to, how a node scans its children's values, when a node is finished, how a finished node's
 // value reaches its parent, what an ancestor's frame word holds.  The LOOPS around them, and where the frames live, are the
 // kernels': the pool's lanes probe a memo, park their searches between launches and cap the returns per iteration; the batch's

@@ -1,7 +1,8 @@
 """Drop-in for reversi_zero/lib/reversi_solver.py (compiled form: lib/alt/reversi_solver_cython.pyx:40-127), backed by
-raz_solve_batch (include/raz.h; kernels in csrc/raz_solver_batch.hip): the exact end-game solver for one position - `solve`, the
-reference's signature and answers - or for arrays of positions at once - `solve_batch`.  Device-only, like the batched functions
-of lib/bitboard.py: there is no CPU fallback, and without a GPU the call raises RuntimeError."""
+raz_solve_batch and raz_solve_exact (include/raz.h; kernels in csrc/raz_solver_batch.hip, raz_solver_exact.hip and the header
+they share, raz_solver_split.h): the exact end-game solver for one position - `solve`, the reference's signature and answers - or
+for arrays of positions at once - `solve_batch`; `solve_exact` / `solve_exact_batch` take deeper positions.  Device-only, like the
+batched functions of lib/bitboard.py: there is no CPU fallback, and without a GPU the call raises RuntimeError."""
 import numpy as np
 
 from .._native import lib, check, tensor_ptr, current_stream_ptr
@@ -59,11 +60,7 @@ class ReversiSolver:
         move (the reference's (None, None)); 2 = refused, more than 14 empty squares; 3 = not a position (a square of both
         colours, a player byte other than 1 / 2); move = -1 and score = -100 where status != 0.  An answer depends on its
         position and the mode alone, never on the rest of the batch."""
-        import torch
-        n = self._check_batch(black, white, next_player, "solve_batch")
-        move = torch.empty(n, dtype=torch.int8, device=black.device)
-        score = torch.empty(n, dtype=torch.int8, device=black.device)
-        status = torch.empty(n, dtype=torch.uint8, device=black.device)
+        n, move, score, status = self._check_batch(black, white, next_player, "solve_batch")
         if n:
             ws = self._workspace(n, black.device)
             check(lib.raz_solve_batch(tensor_ptr(black), tensor_ptr(white), tensor_ptr(next_player), n, int(bool(exactly)),
@@ -73,6 +70,7 @@ class ReversiSolver:
 
     @staticmethod
     def _check_batch(black, white, next_player, what):
+        """The checks of a batch call's arguments; its number of positions and its three outputs (move, score, status)."""
         import torch
         for t in (black, white):
             if t.dtype not in (torch.int64, torch.uint64):
@@ -84,17 +82,15 @@ class ReversiSolver:
         n = black.numel()
         if white.numel() != n or next_player.numel() != n:
             raise ValueError("black, white and next_player must have the same number of elements")
-        return n
+        move, score = (torch.empty(n, dtype=torch.int8, device=black.device) for _ in range(2))
+        return n, move, score, torch.empty(n, dtype=torch.uint8, device=black.device)
 
     def solve_exact_batch(self, black, white, next_player):
         """solve_batch(..., exactly=True) for positions of up to EXACT_MAX_EMPTIES empty squares (raz_solve_exact: the same
         answers, found by a search that passes bounds down): device tensors (move int8, score int8, status uint8); status 2 =
         more than EXACT_MAX_EMPTIES empties.  The call synchronises the current stream (once per group of rounds of the search)."""
         import torch
-        n = self._check_batch(black, white, next_player, "solve_exact_batch")
-        move = torch.empty(n, dtype=torch.int8, device=black.device)
-        score = torch.empty(n, dtype=torch.int8, device=black.device)
-        status = torch.empty(n, dtype=torch.uint8, device=black.device)
+        n, move, score, status = self._check_batch(black, white, next_player, "solve_exact_batch")
         if n:
             empties = 64 - _popcount64(black.view(torch.int64).reshape(-1) | white.view(torch.int64).reshape(-1))
             deepest = int(torch.where(empties <= EXACT_MAX_EMPTIES, empties, torch.zeros_like(empties)).max())
@@ -110,8 +106,8 @@ class ReversiSolver:
                   "raz_solve_exact")
         return move, score, status
 
-    def solve_exact(self, black, white, next_player):
-        """solve(..., exactly=True) for a position of up to EXACT_MAX_EMPTIES empty squares: (move, score) or (None, None)."""
+    def _solve_one(self, batch_call, black, white, next_player, limit, who):
+        """One position through a batch call: (move, score), (None, None) without a legal move, ValueError for what is refused."""
         import torch
         device = torch.device(self._device or "cuda")
         player = _player_byte(next_player)
@@ -121,15 +117,19 @@ class ReversiSolver:
         b = torch.from_numpy(np.array([int(black) & m64], dtype=np.uint64).view(np.int64)).to(device)
         w = torch.from_numpy(np.array([int(white) & m64], dtype=np.uint64).view(np.int64)).to(device)
         p = torch.tensor([player], dtype=torch.uint8, device=device)
-        move, score, status = (int(t.cpu()[0]) for t in self.solve_exact_batch(b, w, p))
+        move, score, status = (int(t.cpu()[0]) for t in batch_call(b, w, p))
         if status == TOO_MANY_EMPTIES:
-            raise ValueError(f"the exact solver takes positions of at most {EXACT_MAX_EMPTIES} empty squares "
+            raise ValueError(f"the {who} takes positions of at most {limit} empty squares "
                              f"(this one has {64 - bin((int(black) | int(white)) & m64).count('1')})")
         if status == NOT_A_POSITION:
             raise ValueError("not a position: a square holds a disc of both colours")
         if status == NO_MOVE:
             return None, None
         return move, score
+
+    def solve_exact(self, black, white, next_player):
+        """solve(..., exactly=True) for a position of up to EXACT_MAX_EMPTIES empty squares: (move, score) or (None, None)."""
+        return self._solve_one(self.solve_exact_batch, black, white, next_player, EXACT_MAX_EMPTIES, "exact solver")
 
     def solve(self, black, white, next_player, timeout=30, exactly=False):
         """ReversiSolver.solve (lib/alt/reversi_solver_cython.pyx:40-61): (move, score) with score the disc difference from the
@@ -140,21 +140,4 @@ class ReversiSolver:
         depends on the host's speed; here the answer is a function of the position and the mode alone.  What the reference could
         only try under its time-out is refused instead: more than 14 empty squares raises ValueError, and so does a position
         with a square of both colours."""
-        import torch
-        device = torch.device(self._device or "cuda")
-        player = _player_byte(next_player)
-        if player not in (1, 2):
-            raise ValueError(f"next_player must be Player.black / Player.white or 1 / 2, not {next_player!r}")
-        m64 = (1 << 64) - 1
-        b = torch.from_numpy(np.array([int(black) & m64], dtype=np.uint64).view(np.int64)).to(device)
-        w = torch.from_numpy(np.array([int(white) & m64], dtype=np.uint64).view(np.int64)).to(device)
-        p = torch.tensor([player], dtype=torch.uint8, device=device)
-        move, score, status = (int(t.cpu()[0]) for t in self.solve_batch(b, w, p, exactly=exactly))
-        if status == TOO_MANY_EMPTIES:
-            raise ValueError(f"the solver takes positions of at most {MAX_EMPTIES} empty squares "
-                             f"(this one has {64 - bin((int(black) | int(white)) & m64).count('1')})")
-        if status == NOT_A_POSITION:
-            raise ValueError("not a position: a square holds a disc of both colours")
-        if status == NO_MOVE:
-            return None, None
-        return move, score
+        return self._solve_one(lambda b, w, p: self.solve_batch(b, w, p, exactly=exactly), black, white, next_player, MAX_EMPTIES, "solver")
