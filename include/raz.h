@@ -498,6 +498,36 @@ size_t raz_solve_exact_workspace_bytes(size_t n, int max_empties);
 int raz_solve_exact(const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player, size_t n, int8_t* d_move,
                     int8_t* d_score, uint8_t* d_status, void* d_workspace, size_t workspace_bytes, uint32_t tuning,
                     raz_stream_t stream);
+/* ---- the win / draw / loss solver (csrc/raz_solver_wld.hip) -----------------------------------------------------------------------
+ * WHO WINS, for positions of up to RAZ_SOLVE_WLD_MAX_EMPTIES empty squares.  The argument list and every convention of
+ * raz_solve_exact carry over: status codes 0 / 1 / 2 / 3 (2 = more than RAZ_SOLVE_WLD_MAX_EMPTIES empties), d_move = -1 and
+ * d_score = -100 where status != 0, the refusals and what they leave unwritten, n == 0, the node-visit counter in the first 8 bytes
+ * of the workspace, the rounds, their groups and the caps on them, the synchronisations.  A solved row answers
+ *   d_score[i]  the OUTCOME o: +1, 0 or -1 - the sign of the game-theoretic disc difference from the side to move's view, under
+ *               ReversiEnv's rules (disc count only);
+ *   d_move[i]   the lowest-numbered legal move whose own outcome for the mover equals o.
+ * Both are functions of the position alone: the other rows, n, the workspace's size, `tuning` and the stream change no output byte.
+ * This is not the move raz_solve_exact returns (the lowest-numbered move of the best DISC DIFFERENCE), nor raz_solve_batch's
+ * exactly = 0 scan.
+ * d_workspace: 256-byte aligned, at least raz_solve_wld_workspace_bytes(n, e) bytes where e >= the most empties of a searched row
+ * (0 is returned for e > RAZ_SOLVE_WLD_MAX_EMPTIES and for n > 2^31: refused).  That size holds the default split of one row in the
+ * worst case - six plies down to 10 empties, and in any case down to 15: at 21 empties 41 664 022 records of 44 bytes, 1.83 GB - and the
+ * parked stacks of the lanes that search.
+ * tuning: raz_solve_exact's word -
+ *   bits 0-4    leaf size (0 = 10; 2..RAZ_SOLVE_WLD_MAX_EMPTIES);
+ *   bits 5-7    the most plies the leaf size is applied for, + 1 (0 = all 6).  Below those plies a node is split only while it has
+ *               more than 15 empty squares: under every tuning one lane's task is a subtree of at most 15 empties;
+ *   bits 8-19   the most rows per chunk (0 = as many as the workspace holds);
+ *   bits 20-23  the node budget of a lane per launch: 0 = 1 024, 1 = 3, 2 = 16, 3 = 128, 4 = 1 024, 5 = 8 192, 6 = 32 768;
+ *   bit 24      children are searched in ascending order (no ordering by the opponent's mobility);
+ *   bit 25      a task's window is not narrowed by what its ancestors have proven (it is still dropped where one is decided);
+ *   bit 26      record cuts off: no task looks at its ancestors, none is dropped, nothing is reported upward;
+ * any other bit, or a value outside those ranges: RAZ_EINVAL. */
+#define RAZ_SOLVE_WLD_MAX_EMPTIES 21
+size_t raz_solve_wld_workspace_bytes(size_t n, int max_empties);
+int raz_solve_wld(const uint64_t* d_black, const uint64_t* d_white, const uint8_t* d_player, size_t n, int8_t* d_move,
+                  int8_t* d_score, uint8_t* d_status, void* d_workspace, size_t workspace_bytes, uint32_t tuning,
+                  raz_stream_t stream);
 /* Diagnostics (no reference counterpart): `bytes` at `offset` of one of the engine's device arrays (raz_engine_device_ptr's numbering:
  * 3 the games' control blocks, 6 the solver blocks, 7 / 8 / 9 the solver pool's lane state / headers / active list) copied to host
  * memory.  RAZ_EINVAL when offset + bytes reaches beyond the array.  Synchronises the device. */

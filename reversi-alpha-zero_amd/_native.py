@@ -165,6 +165,9 @@ SIGNATURES.update({
     "raz_solve_exact_workspace_bytes": (c_size_t, [c_size_t, c_int]),
     "raz_solve_exact": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                         c_uint32, c_void_p]),
+    "raz_solve_wld_workspace_bytes": (c_size_t, [c_size_t, c_int]),
+    "raz_solve_wld": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                      c_uint32, c_void_p]),
     # raznet-train-v1 (csrc/raz_train.hip); the trainer handle travels as c_void_p
     "raz_trainer_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t]),
     "raz_trainer_state_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -10,7 +10,7 @@ from ..agent.player import effective_play_config
 from ..engine import (ANALYSIS_ENTRY_END, ANALYSIS_ENTRY_PASS, ANALYSIS_MAX_MOVES, EVAL_SOLVED, POS_OVER, POS_PASS_ENTRY, POS_SEARCH,
                       DeviceAnalysis, DeviceNet, SelfPlayEngine)
 from .ggf import convert_to_bitboard_and_actions, parse_ggf
-from .reversi_solver import EXACT_MAX_EMPTIES
+from .reversi_solver import EXACT_MAX_EMPTIES, WLD_MAX_EMPTIES
 
 logger = getLogger(__name__)
 
@@ -110,11 +110,78 @@ def annotate_exact(games, exact_empties, solver, device="cuda:0"):
     return games
 
 
+def annotate_wld(games, wld_empties, solver, exact_empties=None, device="cuda:0"):
+    """Adds the win / draw / loss solver's verdicts to analyze()'s dictionaries, in place: every position of state `search` or
+    `pass_entry` with at most `wld_empties` empty squares that `exact_empties` does not already cover goes through ONE
+    solver.solve_wld_batch call, and the positions after their played moves through one more.  Such a position gets solved_outcome
+    (+1 / 0 / -1, the side to move's view), outcome_move (the lowest-numbered move of that outcome) and, where a move was played,
+    played_outcome - the outcome of that move: the next position's, negated when the mover changed, or the sign of the final disc
+    difference seen from the mover - and outcome_kept = (played_outcome == solved_outcome).  A pass entry whose side to move cannot
+    move takes the outcome of the position after it."""
+    import torch
+    if not (isinstance(wld_empties, int) and 1 <= wld_empties <= WLD_MAX_EMPTIES):
+        raise ValueError(f"wld_empties must be 1..{WLD_MAX_EMPTIES}, not {wld_empties!r}")
+    covered = exact_empties if exact_empties is not None else 0
+    rows = [(g, i) for g, game in enumerate(games) for i, d in enumerate(game)
+            if d["state"] in ("search", "pass_entry") and covered < _empties(d) <= wld_empties]
+    if not rows:
+        return games
+    u = lambda xs: torch.from_numpy(np.array(xs, dtype=np.uint64).view(np.int64)).to(device)   # noqa: E731
+
+    def batch(where):
+        got = solver.solve_wld_batch(u([games[g][i]["black"] for g, i in where]), u([games[g][i]["white"] for g, i in where]),
+                                     torch.tensor([games[g][i]["player"] for g, i in where], dtype=torch.uint8, device=device))
+        return [np.asarray(t.cpu()) for t in got]
+
+    sign = lambda v: (v > 0) - (v < 0)   # noqa: E731
+    move, outcome, status = batch(rows)
+    must_pass = set()
+    for k, (g, i) in enumerate(rows):
+        if status[k] == 0:
+            games[g][i].update(solved_outcome=int(outcome[k]), outcome_move=int(move[k]))
+        elif status[k] == 1:
+            must_pass.add((g, i))
+        else:
+            raise ValueError(f"game {g}, position {i}: the win/draw/loss solver answered status {int(status[k])}")
+    after = [(g, i + 1) for g, i in rows if games[g][i]["played"] is not None and games[g][i + 1]["state"] != "over"]
+    played = {}
+    if after:
+        _, o2, s2 = batch(after)
+        played = {where: int(o2[k]) for k, where in enumerate(after) if s2[k] == 0}
+
+    def known(d, player):
+        """The outcome of a position that is finished or annotated already, seen from `player`; None where it is not known."""
+        if d["state"] == "over":
+            v = d.get("disc_diff")
+        else:
+            v = d.get("solved_outcome", d.get("solved_score"))
+        return None if v is None else (sign(v) if d["player"] == player else -sign(v))
+
+    for g, game in enumerate(games):
+        for i in range(len(game) - 1, -1, -1):   # backwards: a position's successor is finished first
+            d = game[i]
+            if (g, i) in must_pass and i + 1 < len(game):
+                v = known(game[i + 1], d["player"])
+                if v is not None:
+                    d.update(solved_outcome=v, outcome_move=None)
+            if "solved_outcome" in d and d["played"] is not None and i + 1 < len(game):
+                nxt = game[i + 1]
+                if (g, i + 1) in played:
+                    v = played[(g, i + 1)] if nxt["player"] == d["player"] else -played[(g, i + 1)]
+                else:   # the game is over there, or that side cannot move: what is known of it already
+                    v = known(nxt, d["player"])
+                if v is not None:
+                    d.update(played_outcome=v, outcome_kept=bool(v == d["solved_outcome"]))
+    return games
+
+
 class GameAnalyzer:
     """analyze(games): per game a list of per-position dictionaries - moves_made, player (side to move), eval (the most visited
     move's value, from the side to move's view), best_move, visits, top; played_eval / played_diff for the move that was played;
     exact where the end-game solver answered.  analyze(games, exact_empties=k) adds annotate_exact's fields for the positions of
-    at most k empty squares (`solver`: the object whose solve_exact_batch answers them; None = a ReversiSolver, built when first needed)."""
+    at most k empty squares (`solver`: the object whose solve_exact_batch answers them; None = a ReversiSolver, built when first needed).
+    analyze(games, wld_empties=m) adds annotate_wld's fields - who wins - for the positions of at most m empty squares that
+    exact_empties does not cover (the same solver object's solve_wld_batch)."""
 
     def __init__(self, config, model, play_config=None, slots=1024, device="cuda:0", seed=0, solver=None):
         self.solver = solver
@@ -138,8 +205,10 @@ class GameAnalyzer:
         if eng.pool_nearly_full(st, STEPS_PER_COLLECT * COLLECTS_PER_STATS):
             eng.gc(threshold=min(int(eng.cfg.nodes_per_game) // 4, st["max_pool_used"] // 2))
 
-    def analyze(self, games, exact_empties=None):
+    def analyze(self, games, exact_empties=None, wld_empties=None):
         import torch
+        if wld_empties is not None and not (isinstance(wld_empties, int) and 1 <= wld_empties <= WLD_MAX_EMPTIES):
+            raise ValueError(f"wld_empties must be 1..{WLD_MAX_EMPTIES}, not {wld_empties!r}")
         if exact_empties is not None and not (isinstance(exact_empties, int) and 1 <= exact_empties <= EXACT_MAX_EMPTIES):
             raise ValueError(f"exact_empties must be 1..{EXACT_MAX_EMPTIES}, not {exact_empties!r}")
         games = [game_from_ggf(g) if isinstance(g, str) else tuple(g) for g in games]
@@ -175,9 +244,11 @@ class GameAnalyzer:
             _, p, e = an.results()
             out += [positions_of(p[i], e[i]) for i in range(len(chunk))]
             self.passes += 1
+        if (exact_empties is not None or wld_empties is not None) and self.solver is None:
+            from .reversi_solver import ReversiSolver
+            self.solver = ReversiSolver(self.device)
         if exact_empties is not None:
-            if self.solver is None:
-                from .reversi_solver import ReversiSolver
-                self.solver = ReversiSolver(self.device)
             annotate_exact(out, exact_empties, self.solver, self.device)
+        if wld_empties is not None:
+            annotate_wld(out, wld_empties, self.solver, exact_empties, self.device)
         return out

@@ -1,7 +1,8 @@
 """Drop-in for reversi_zero/lib/reversi_solver.py (compiled form: lib/alt/reversi_solver_cython.pyx:40-127), backed by
 raz_solve_batch and raz_solve_exact (include/raz.h; kernels in csrc/raz_solver_batch.hip, raz_solver_exact.hip and the header
 they share, raz_solver_split.h): the exact end-game solver for one position - `solve`, the reference's signature and answers - or
-for arrays of positions at once - `solve_batch`; `solve_exact` / `solve_exact_batch` take deeper positions.  Device-only, like the
+for arrays of positions at once - `solve_batch`; `solve_exact` / `solve_exact_batch` take deeper positions, and `solve_wld` /
+`solve_wld_batch` (raz_solve_wld, csrc/raz_solver_wld.hip) answer who wins for deeper ones still.  Device-only, like the
 batched functions of lib/bitboard.py: there is no CPU fallback, and without a GPU the call raises RuntimeError."""
 import numpy as np
 
@@ -10,6 +11,8 @@ from .._native import lib, check, tensor_ptr, current_stream_ptr
 MAX_EMPTIES = 14   # the library's declared limit: below turn 46 the reference leans on its 30 s wall-clock time-out
 
 EXACT_MAX_EMPTIES = 17   # raz_solve_exact's limit (RAZ_SOLVE_EXACT_MAX_EMPTIES): the full scan's answer, found with bounds passed down
+
+WLD_MAX_EMPTIES = 21   # raz_solve_wld's limit (RAZ_SOLVE_WLD_MAX_EMPTIES): who wins, and the lowest-numbered move of that outcome
 
 SOLVED, NO_MOVE, TOO_MANY_EMPTIES, NOT_A_POSITION = 0, 1, 2, 3
 
@@ -41,6 +44,7 @@ class ReversiSolver:
         self._device = device
         self._ws = None   # the workspace of raz_solve_batch: owned here, grown when a batch needs more, reused otherwise
         self._ws_exact = None   # the workspace of raz_solve_exact, likewise
+        self._ws_wld = None   # the workspace of raz_solve_wld, likewise
 
     def _workspace(self, n, device):
         import torch
@@ -106,6 +110,28 @@ class ReversiSolver:
                   "raz_solve_exact")
         return move, score, status
 
+    def solve_wld_batch(self, black, white, next_player):
+        """Who wins, for positions of up to WLD_MAX_EMPTIES empty squares (raz_solve_wld): device tensors (move int8, outcome int8,
+        status uint8); outcome = +1 / 0 / -1, the sign of the game-theoretic disc difference from the side to move's view, move =
+        the lowest-numbered legal move of that outcome; status as solve_batch, 2 = more than WLD_MAX_EMPTIES empties.  The call
+        synchronises the current stream (once per group of rounds of the search)."""
+        import torch
+        n, move, outcome, status = self._check_batch(black, white, next_player, "solve_wld_batch")
+        if n:
+            empties = 64 - _popcount64(black.view(torch.int64).reshape(-1) | white.view(torch.int64).reshape(-1))
+            deepest = int(torch.where(empties <= WLD_MAX_EMPTIES, empties, torch.zeros_like(empties)).max())
+            want = lib.raz_solve_wld_workspace_bytes(n, deepest)
+            if want == 0:
+                raise ValueError(f"raz_solve_wld refuses a batch of {n} positions")
+            want += min(n * 65536, 1 << 31)   # room for whole rows to share a pass
+            ws = self._ws_wld
+            if ws is None or ws.numel() < want or ws.device != black.device:
+                ws = self._ws_wld = torch.empty(want, dtype=torch.uint8, device=black.device)
+            check(lib.raz_solve_wld(tensor_ptr(black), tensor_ptr(white), tensor_ptr(next_player), n, tensor_ptr(move),
+                                    tensor_ptr(outcome), tensor_ptr(status), tensor_ptr(ws), ws.numel(), 0, current_stream_ptr()),
+                  "raz_solve_wld")
+        return move, outcome, status
+
     def _solve_one(self, batch_call, black, white, next_player, limit, who):
         """One position through a batch call: (move, score), (None, None) without a legal move, ValueError for what is refused."""
         import torch
@@ -130,6 +156,10 @@ class ReversiSolver:
     def solve_exact(self, black, white, next_player):
         """solve(..., exactly=True) for a position of up to EXACT_MAX_EMPTIES empty squares: (move, score) or (None, None)."""
         return self._solve_one(self.solve_exact_batch, black, white, next_player, EXACT_MAX_EMPTIES, "exact solver")
+
+    def solve_wld(self, black, white, next_player):
+        """Who wins a position of up to WLD_MAX_EMPTIES empty squares: (move, outcome) or (None, None)."""
+        return self._solve_one(self.solve_wld_batch, black, white, next_player, WLD_MAX_EMPTIES, "win/draw/loss solver")
 
     def solve(self, black, white, next_player, timeout=30, exactly=False):
         """ReversiSolver.solve (lib/alt/reversi_solver_cython.pyx:40-61): (move, score) with score the disc difference from the
